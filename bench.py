@@ -9,11 +9,18 @@ round-robin shard k = r (mod N) of a global batch of N x 4M fragments (weak scal
 collective on the data path; torch.distributed is used only for the barrier and the
 max-over-ranks time).
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the last
+step's checksums if --dump-outputs is given, and prints the result line; `cpu_baseline` and `parity`
+are null.  --full adds those two legs (a --dry-run, whose whole point is the parity check, always
+carries it).
+
 Prints ONE JSON line (rank 0):
   value      = bytes checksummed by all ranks / max-over-ranks wall time of the K steps, GiB/s
+  ms_per_step = that wall time / K, in milliseconds
   roofline   = dominant kernel's algorithmic bytes per launch (= 16 GiB payload) / its
                average launch duration from HIP events on the launch stream, vs 8.0 TB/s
-  cpu_baseline = the reference's uicrc (oracle/_ref, compiled from /root/reference) or the
+--full only:
+  cpu_baseline = the reference's uicrc (oracle/_ref, compiled from the reference's sources) or the
                clean-room port, on this host's cores (1 and the affinity mask), over BASELINE
                config A exactly (seed 1, 1M x 1 KiB), digest-checked
   parity     = digest of all ranks' results (global fragment indices) vs committed digests
@@ -26,7 +33,14 @@ GPU).  Every rank's kernel average is gathered into `per_gpu` (GiB/s and rooflin
 GPU) and `aggregate` (all bytes / slowest kernel / N x 8 TB/s).  A node with fewer GPUs than
 ranks fails loudly.
 
+--dump-outputs DIR writes what the timed path returned in its last step, the per-fragment checksums,
+as DIR/checksums.npy (float64, exact for 32-bit values; DIR/checksums_rank<r>.npy per rank with
+N > 1; a fixed seeded sample where all ranks' values would exceed 64 MB).  The payload is generated
+from the seed, so two builds run with the same arguments can be compared value for value.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--frags F] [--frag-bytes L]
+       python bench.py --full                # + cpu_baseline and parity
+       python bench.py --dump-outputs DIR    # + DIR/checksums.npy
        python bench.py --config D --gpus N   # 32M x 16 KiB over N >= 4 GPUs (<= 200 GiB per rank)
        python bench.py --config D --shard g  # GPU g's full 64 GiB shard of the 8-GPU partition, 1 GPU
        python bench.py --gpus 2 --dry-run    # CPU rehearsal of the rank launch (gloo, no kernel)
@@ -98,7 +112,13 @@ def parse():
     ap.add_argument("--frag-bytes", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=2)
     ap.add_argument("--mode", choices=["crc", "sum"], default="crc")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and the parity check "
+                         "of the results against the committed digests (exit 3 if they differ)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's per-fragment checksums as "
+                         "DIR/checksums.npy (float64; at most 64 MB over all ranks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--config", choices=["B", "C", "D"], default="B",
                     help="B: 4M x 4 KiB per GPU, seed 2 (default, weak scaling); "
                          "C: mixed 64 B - 64 KiB Zipf sizes, >= 4 GiB, seed 5 (1 GPU, descriptor batch); "
@@ -133,6 +153,9 @@ def parse():
         ap.error("LAMPI_BENCH_BACKEND must be nccl or gloo")
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.dump_outputs is not None and (args.dry_run or args.e2e or args.latency or args.bcopy or args.recv
+                                          or args.config == "C"):
+        ap.error("--dump-outputs covers the device-resident uniform configs (B, D)")
     if args.frags is None:
         args.frags = (1024 // args.gpus) if args.dry_run else 4194304
     return args
@@ -258,6 +281,27 @@ def gather_rows(row, world: int, args) -> list:
     parts = [torch.empty_like(t) for _ in range(world)]
     dist.all_gather(parts, t)
     return [p.cpu().tolist() for p in parts]
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(path: str, vals, rank: int, world: int) -> dict:
+    """Write this rank's per-fragment checksums (uint32) as float64 -- every 32-bit value exact -- to
+    DIR/checksums.npy (checksums_rank<r>.npy with several ranks).  A rank whose share of DUMP_MAX_BYTES does
+    not hold them all writes the values at a fixed seeded sample of ascending positions instead."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // world // 8 - 16  # float64 values per rank, less the .npy header
+    sampled = vals.size > cap
+    if sampled:
+        vals = vals[np.sort(np.random.default_rng(0).choice(vals.size, size=cap, replace=False))]
+    name = "checksums.npy" if world == 1 else f"checksums_rank{rank}.npy"
+    np.save(os.path.join(path, name), vals.astype(np.float64))
+    return {"file": name, "dtype": "float64", "values": int(vals.size),
+            "what": "the last timed step's per-fragment checksums" +
+                    (" at a fixed sample of positions (numpy default_rng(0), ascending)" if sampled else "")}
 
 
 def cpu_baseline():
@@ -568,38 +612,42 @@ def run_device(args):
         vals = dv.as_u32(out)
     kern_avg_s = sum(kern_ms) / len(kern_ms) / 1e3
 
-    # parity: this rank's shard digest (global fragment indices), combined over the ranks, vs
-    # committed digests
-    local = shard.digest(vals, ks) if vals is not None else tuple(shard_dig)
-    if args.dry_run and args.config == "D":
-        whole = shard.allreduce_digest(local) if world > 1 else local
-        want = golden_digest(seed, n_global, L, crc)
-        check = "dry run: committed per-shard digests combined over the ranks vs the whole-batch digest"
-    elif args.dry_run:
-        whole = shard.allreduce_digest(local) if world > 1 else local
-        want = tuple(head["digest_crc" if crc else "digest_sum"]) if n_global == head["n"] else None
-        check = "combined shard digests vs tests/golden/config_b_head.json (reference values)"
-    elif args.shard is not None:
-        whole = local
-        want = shard_golden(seed, n_global, L, crc, 8, args.shard)
-        check = f"config D shard {args.shard} of 8 (64 GiB): digest vs tests/golden/bench_digests.json" + \
-                (" and BASELINE.md per-GPU XOR" if crc else "")
-        if want is not None and crc and want[0] != CONFIG_D_SHARD_XOR[args.shard]:
-            raise SystemExit("tests/golden/bench_digests.json disagrees with BASELINE.md")
-    else:
-        whole = shard.allreduce_digest(local) if world > 1 else local
-        want = golden_digest(seed, n_global, L, crc)
-        check = "full digest vs BASELINE.md / tests/golden/bench_digests.json"
-    if want is not None:
-        ok = whole == tuple(want)
-        if args.config == "D" and world == 8 and crc:
-            ok = ok and local[0] == CONFIG_D_SHARD_XOR[rank]
-            check += " (per-GPU shard XOR too)"
-        parity = {"check": check, "xor": f"{whole[0]:08x}", "wsum": f"{whole[1]:08x}", "ok": ok}
-    else:
-        parity = {"check": "no committed digest for this shape (tests/golden/make_bench_digests.py)",
-                  "xor": f"{whole[0]:08x}", "wsum": f"{whole[1]:08x}", "ok": None}
-    bad = 0 if parity["ok"] is not False else 1
+    dumped = dump_outputs(args.dump_outputs, vals, rank, world) if args.dump_outputs is not None else None
+
+    parity = None  # --full (and every dry run)
+    if args.full or args.dry_run:
+        # parity: this rank's shard digest (global fragment indices), combined over the ranks, vs
+        # committed digests
+        local = shard.digest(vals, ks) if vals is not None else tuple(shard_dig)
+        if args.dry_run and args.config == "D":
+            whole = shard.allreduce_digest(local) if world > 1 else local
+            want = golden_digest(seed, n_global, L, crc)
+            check = "dry run: committed per-shard digests combined over the ranks vs the whole-batch digest"
+        elif args.dry_run:
+            whole = shard.allreduce_digest(local) if world > 1 else local
+            want = tuple(head["digest_crc" if crc else "digest_sum"]) if n_global == head["n"] else None
+            check = "combined shard digests vs tests/golden/config_b_head.json (reference values)"
+        elif args.shard is not None:
+            whole = local
+            want = shard_golden(seed, n_global, L, crc, 8, args.shard)
+            check = f"config D shard {args.shard} of 8 (64 GiB): digest vs tests/golden/bench_digests.json" + \
+                    (" and BASELINE.md per-GPU XOR" if crc else "")
+            if want is not None and crc and want[0] != CONFIG_D_SHARD_XOR[args.shard]:
+                raise SystemExit("tests/golden/bench_digests.json disagrees with BASELINE.md")
+        else:
+            whole = shard.allreduce_digest(local) if world > 1 else local
+            want = golden_digest(seed, n_global, L, crc)
+            check = "full digest vs BASELINE.md / tests/golden/bench_digests.json"
+        if want is not None:
+            ok = whole == tuple(want)
+            if args.config == "D" and world == 8 and crc:
+                ok = ok and local[0] == CONFIG_D_SHARD_XOR[rank]
+                check += " (per-GPU shard XOR too)"
+            parity = {"check": check, "xor": f"{whole[0]:08x}", "wsum": f"{whole[1]:08x}", "ok": ok}
+        else:
+            parity = {"check": "no committed digest for this shape (tests/golden/make_bench_digests.py)",
+                      "xor": f"{whole[0]:08x}", "wsum": f"{whole[1]:08x}", "ok": None}
+    bad = 1 if parity is not None and parity["ok"] is False else 0
     # per-rank rows: [kernel avg s, bytes, parity failure, local wall s]
     rows = gather_rows([kern_avg_s, float(n) * L, float(bad), t1 - t0], world, args)
 
@@ -612,7 +660,7 @@ def run_device(args):
         per_gpu = [{"rank": i, "bytes": int(r[1]), "kernel_avg_ms": round(r[0] * 1e3, 4),
                     "GiB_per_s": round(r[1] / GIB / r[0], 2),
                     "roofline_frac": round(r[1] / r[0] / 1e9 / HBM_PEAK_GBS, 4),
-                    "parity_ok": r[2] == 0} for i, r in enumerate(rows)]
+                    "parity_ok": None if parity is None else r[2] == 0} for i, r in enumerate(rows)]
         # PMC traffic is recorded per kernel: the descriptor runs have no entry of their own
         cfg_key = f"{'crc' if crc else 'sum'}_{'desc_' if args.desc else ''}{n}x{L}"
         traffic = None if args.dry_run else read_traffic(cfg_key)
@@ -666,14 +714,16 @@ def run_device(args):
             "aggregate": {"GiB_per_s_kernel": round(bytes_total / GIB / kmax, 2),
                           "roofline_frac": round(bytes_total / kmax / 1e9 / (HBM_PEAK_GBS * world), 4),
                           "note": "sum of all ranks' bytes / slowest rank's kernel average / (N x 8 TB/s)"},
-            "parity": {**parity, "all_ranks_ok": all(r[2] == 0 for r in rows)},
+            "parity": None if parity is None else {**parity, "all_ranks_ok": all(r[2] == 0 for r in rows)},
         }
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if args.dry_run:
             result["dry_run"] = True
         if args.share_gpu and world > 1:
             result["rehearsal"] = (f"{world} ranks shared the visible GPU(s) (LAMPI_BENCH_SHARE_GPU=1, backend "
                                    f"{args.backend}): checks the N-rank flow; the numbers are not a scaling result")
-        if world == 1 and not args.no_cpu_baseline and not args.dry_run and args.shard is None:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dry_run and args.shard is None:
             result["cpu_baseline"] = cpu_baseline()
         else:
             result["cpu_baseline"] = None
@@ -1362,7 +1412,7 @@ def main():
         import torch.distributed as dist
 
         dist.destroy_process_group()
-    if result is not None and not result["parity"]["all_ranks_ok"]:
+    if result is not None and result["parity"] is not None and not result["parity"]["all_ranks_ok"]:
         sys.exit(3)  # a rank's checksums differ from the committed digests
 
 

@@ -6,6 +6,8 @@ environment), they rendezvous over gloo on 127.0.0.1, take their round-robin sha
 the same code path a GPU run takes, with the kernel replaced by the reference's committed
 values (tests/golden/config_b_head.json).  The combined digest is checked here against the
 oracle, independently of that file.
+
+One GPU test: a plain run is lean (no CPU baseline, no parity leg) and --dump-outputs holds its checksums.
 """
 import json
 import os
@@ -141,6 +143,48 @@ def test_config_d_shard_digests_committed():
         ws = (ws + got[1]) & 0xFFFFFFFF
         assert bench.shard_golden(3, 33554432, 16384, False, 8, g) is not None
     assert (xs, ws) == (0xF2A5DDAD, 0x3383EB2F)  # BASELINE.md config D total
+
+
+def test_dump_outputs_exact_capped_and_repeatable(tmp_path):
+    """--dump-outputs: float64 holds every 32-bit checksum exactly; all ranks' files stay within 64 MB, a rank
+    over its share writing the same ascending sample of positions every time."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    vals = np.array([0, 1, 0x9AFF1C82, 0xFFFFFFFF], dtype=np.uint32)
+    info = bench.dump_outputs(str(tmp_path / "a"), vals, 0, 1)
+    got = np.load(tmp_path / "a" / "checksums.npy")
+    assert info["file"] == "checksums.npy" and got.dtype == np.float64
+    assert np.array_equal(got.astype(np.uint32), vals)
+    big = (np.arange(5000000, dtype=np.uint64) * 2654435761 & 0xFFFFFFFF).astype(np.uint32)
+    for d in ("b", "c"):
+        for r in range(2):
+            bench.dump_outputs(str(tmp_path / d), big, r, 2)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["checksums_rank0.npy", "checksums_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= bench.DUMP_MAX_BYTES
+    b0, c0 = np.load(tmp_path / "b" / files[0]), np.load(tmp_path / "c" / files[0])
+    assert np.array_equal(b0, c0) and b0.size < big.size
+    pos = np.sort(np.random.default_rng(0).choice(big.size, size=b0.size, replace=False))
+    assert np.array_equal(b0.astype(np.uint32), big[pos])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_checksums(cuda, oracle, tmp_path):
+    """A plain run carries the headline figure and ms_per_step but neither the CPU baseline nor the parity leg,
+    --steps sets the timed steps, and --dump-outputs holds what lampi_msg_csum returned in the last step."""
+    n = 1024
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--frags", str(n), "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert d["steps"] == 3 and len(d["per_gpu"]) == 1
+    assert d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "GiB/s" and d["higher_is_better"] is True
+    # value is the payload over one timed step (both rounded: ms_per_step to 1e-4 ms, value to 0.01)
+    assert abs(d["value"] - n * 4096 / 2**30 / (d["ms_per_step"] / 1e3)) <= d["value"] * 1e-4 / d["ms_per_step"] + 0.01
+    assert d["cpu_baseline"] is None and d["parity"] is None
+    got = np.load(tmp_path / "checksums.npy")
+    assert got.dtype == np.float64 and d["dumped_outputs"]["values"] == n
+    assert np.array_equal(got.astype(np.uint32), oracle.uniform_batch(2, 0, n, 4096, 0))
 
 
 def test_shard_indices_match_fill_layout():

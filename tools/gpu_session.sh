@@ -27,12 +27,12 @@ for step in "$@"; do
   case $step in
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
-    bench) run bench 600 python bench.py ;;
-    bench16k) run bench16k 600 python bench.py --frags 1048576 --frag-bytes 16384 --no-cpu-baseline ;;
-    benchsum) run benchsum 600 python bench.py --mode sum --no-cpu-baseline ;;
+    bench) run bench 600 python bench.py --full ;;
+    bench16k) run bench16k 600 python bench.py --frags 1048576 --frag-bytes 16384 --full --no-cpu-baseline ;;
+    benchsum) run benchsum 600 python bench.py --mode sum --full --no-cpu-baseline ;;
     benchC) run benchC 600 python bench.py --config C --steps 50 ;;
     benchCsum) run benchCsum 600 python bench.py --config C --mode sum --steps 50 ;;
-    benchD) run benchD 600 python bench.py --desc --no-cpu-baseline ;;
+    benchD) run benchD 600 python bench.py --desc --full --no-cpu-baseline ;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run \
             -- python3 bench.py --steps 20 --no-cpu-baseline ;;
     pmc) run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o run \
@@ -81,12 +81,12 @@ for step in "$@"; do
     gm) for m in crc sum; do  # GM's 65,456-byte payloads, with and without LAMPI_CSUM_ROWS_HINT(16)
           for h in 0 16; do
             run gm_recv_${m}_h$h 600 python bench.py --recv --mode $m --frags 16384 --frag-bytes 65456 --rows-hint $h --steps 20 --warmup 60 &&
-            run gm_desc_${m}_h$h 600 python bench.py --desc --mode $m --frags 16404 --frag-bytes 65456 --rows-hint $h --steps 20 --warmup 60 --no-cpu-baseline
+            run gm_desc_${m}_h$h 600 python bench.py --desc --mode $m --frags 16404 --frag-bytes 65456 --rows-hint $h --steps 20 --warmup 60 --full --no-cpu-baseline
           done
         done ;;
     bigdesc) for spec in 16404:65456:16 1024:1048576:256 256:4194304:1024; do  # read-only, LAMPI_CSUM_ROWS_HINT
                IFS=: read -r nf fb h <<< "$spec"
-               run desc_${fb}_h$h 600 python bench.py --desc --frags $nf --frag-bytes $fb --rows-hint $h --steps 20 --warmup 60 --no-cpu-baseline
+               run desc_${fb}_h$h 600 python bench.py --desc --frags $nf --frag-bytes $fb --rows-hint $h --steps 20 --warmup 60 --full --no-cpu-baseline
              done &&
              run prof_desc_gm 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_desc_gm -o run \
                -- python3 bench.py --desc --frags 16404 --frag-bytes 65456 --rows-hint 16 --steps 20 --warmup 60 --no-cpu-baseline &&
