@@ -390,6 +390,63 @@ int lampi_msg_bcopy(const void *d_msg, size_t msg_len, size_t frag_len, void *d_
 int lampi_msg_bcopy_strided(const void *d_msg, size_t msg_len, size_t frag_len, void *d_dst, size_t dst_stride,
                             uint32_t partial, void *d_out, size_t out_stride, int mode, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * The send step in one call: payload copy, dataChecksum and the header checksum.
+ *
+ * The reference packs a fragment in one place (src/path/gm/sendFrag.cc:143-226,
+ * src/path/ib/sendFrag.cc:119-138, :289-320): the payload goes into the NIC buffer with the
+ * checksum fused, that value v is stored in dataChecksum, then the 68 header bytes that now
+ * hold it are checksummed into `checksum`.  The 72-byte data header is the same for
+ * gmHeaderData and ibDataHdr_t (gm/header.h:56-70, ib/header.h:48-62): dataLength u32 @20,
+ * frag_seq u64 @32, sendFragDescPtr u64 @48, dataSeqOffset u64 @56, dataChecksum u32 @64,
+ * checksum u32 @68.  (Quadrics' 128-byte header is not covered.)
+ *
+ * hdr_kind says what the two words get; v = bcopy_uicrc / bcopy_uicsum of the fragment, H = the
+ * header's first 68 bytes with the word @64 already stored:
+ *   LAMPI_SEND_HDR_GM (gm/sendFrag.cc:134, :147-155, :219-225)
+ *     CRC32 / SUM32: @64 = v; @68 = BasePath_t::headerChecksum(H, 68, 18) with the word @68 taken
+ *                    as 0 (as :134 leaves it): bswap32(uicrc(H, 68)), or the sum of words 0..16.
+ *     NONE:          the payload is copied, neither word is written.
+ *   LAMPI_SEND_HDR_IB (ib/sendFrag.cc:119-138, :306-314)
+ *     CRC32 / SUM32: @64 = v, or 0 for a fragment of length 0 (max(copylen, csumlen) == 0);
+ *                    @68 = uicrc(H, 68) as it is (not swapped), or uicsum(H, 68) of a fresh state.
+ *     NONE:          the payload is copied, @64 = 0 and @68 = 0.
+ * ---------------------------------------------------------------------------------- */
+enum lampi_send_hdr_kind {
+    LAMPI_SEND_HDR_GM = 0,
+    LAMPI_SEND_HDR_IB = 1
+};
+
+/* Descriptor form.  Header i is at (char *)d_hdrs + i*hdr_stride (d_hdrs and hdr_stride 4-byte aligned,
+ * hdr_stride >= 72) and its bytes [0, 64) are already filled; descriptor i is a lampi_copy_desc as for
+ * lampi_frag_bcopy_batch (dst normally header + 72, any address outside every header allowed; copylen /
+ * csumlen with bcopy semantics; partial honoured in CRC mode).  mode takes LAMPI_CSUM_ROWS_HINT bits as
+ * lampi_frag_bcopy_batch_strided does.  Apart from the copies exactly the words named above are written.
+ * No allocation and no scatter launch: the wave (or join thread) that finishes a fragment stamps its header,
+ * as lampi_copy_to_app_batch gives its verdict -- except CRC batches of IB-sized fragments or of row groups,
+ * which measured faster as the copy kernels plus one stamp launch over pooled scratch.
+ * n == 0 returns 0.  d_hdrs may be NULL only for GM with LAMPI_CSUM_NONE (nothing is written there). */
+int lampi_send_pack_batch(const lampi_copy_desc *d_descs, size_t n, void *d_hdrs, size_t hdr_stride,
+                          int hdr_kind, int mode, void *stream);
+
+/* Message form: the whole header is built on the device.  Slot k's 72 bytes are tmpl with
+ * @20 = fragment k's length, @32 = frag_seq0 + k*frag_seq_step, @48 = desc_ptr0 + k*desc_ptr_stride,
+ * @56 = seq_offset0 + k*frag_len, and @64 / @68 by the table above (with LAMPI_CSUM_NONE: GM keeps tmpl's
+ * word @64 and stores 0 @68, IB stores 0 in both). */
+typedef struct lampi_send_hdr_fill {
+    uint8_t  tmpl[72];                      /* constant fields; the varying ones are overwritten */
+    uint64_t frag_seq0, frag_seq_step;
+    uint64_t desc_ptr0, desc_ptr_stride;
+    uint64_t seq_offset0;
+} lampi_send_hdr_fill;                      /* HOST memory, read during the call */
+
+/* Fragments d_msg as lampi_msg_csum does (msg_len == 0: one empty fragment, its header still written),
+ * copies fragment k to d_ring + k*slot_stride + 72 with its checksum fused (every fragment from
+ * CRC_INITIAL_REGISTER / a fresh state) and writes all 72 header bytes at d_ring + k*slot_stride.
+ * d_ring and slot_stride 8-byte aligned, slot_stride >= 72 + frag_len, 1 <= frag_len <= 2^32 - 1. */
+int lampi_msg_send_pack(const void *d_msg, size_t msg_len, size_t frag_len, void *d_ring, size_t slot_stride,
+                        const lampi_send_hdr_fill *h_fill, int hdr_kind, int mode, void *stream);
+
 /* Fragments a contiguous device-resident message the way the path layer does
  * (fragment k = bytes [k*frag_len, min((k+1)*frag_len, msg_len)),
  * src/path/gm/path.cc:98-121) and writes ceil(msg_len/frag_len) checksums to d_out.

@@ -76,6 +76,19 @@ class HostPiece(ctypes.Structure):
 
 assert ctypes.sizeof(HostPiece) == 32
 
+HDR_GM = 0  # enum lampi_send_hdr_kind (include/lampi_csum.h)
+HDR_IB = 1
+
+
+class SendHdrFill(ctypes.Structure):
+    """struct lampi_send_hdr_fill (112 bytes): the 72-byte header template and the per-fragment series."""
+
+    _fields_ = [("tmpl", ctypes.c_uint8 * 72), ("frag_seq0", ctypes.c_uint64), ("frag_seq_step", ctypes.c_uint64),
+                ("desc_ptr0", ctypes.c_uint64), ("desc_ptr_stride", ctypes.c_uint64), ("seq_offset0", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(SendHdrFill) == 112
+
 _lock = threading.Lock()
 _lib = None
 
@@ -111,6 +124,10 @@ PROTOTYPES = {
     "lampi_frag_bcopy_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_int, c_void_p]),
     "lampi_msg_bcopy_strided": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, ctypes.c_uint32,
                                                c_void_p, c_size_t, ctypes.c_int, c_void_p]),
+    "lampi_send_pack_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_int, ctypes.c_int,
+                                             c_void_p]),
+    "lampi_msg_send_pack": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.c_int,
+                                           ctypes.c_int, c_void_p]),
     "lampi_chain_csum_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
                                                       ctypes.c_int, c_void_p]),
     "lampi_header_csum_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, ctypes.c_uint32, ctypes.c_uint32,

@@ -124,7 +124,9 @@ struct FragInfo {
     uint8_t *dst;      // copy sources only: destination of the first copylen bytes
     uint32_t copylen;
     uint32_t aux = 0;  // receive sources: the expected checksum, loaded with the descriptor so its
-                       // latency hides under the fragment's rows (emit compares against it)
+                       // latency hides under the fragment's rows (emit compares against it); send sources:
+                       // the header's prefix (send_hdr_prefix)
+    uint32_t lazy = 0;  // send sources in the join kernels: aux not computed, the emitting lane takes it
 };
 
 // ---- fragment sources (wave-uniform) ----------------------------------------------
@@ -384,6 +386,142 @@ struct IsRecv<RecvSource> : std::true_type {};
 template <>
 struct IsRecv<RecvCopyOnlySource> : std::true_type {};
 
+// ---- the send step's header stamp (lampi_send_pack_batch / lampi_msg_send_pack) ------------------------
+// The 72-byte data header of gmHeaderData / ibDataHdr_t (ref src/path/gm/header.h:56-70, src/path/ib/header.h:48-62):
+// dataChecksum @64, checksum @68.  The reference stores the fused copy's value v in dataChecksum and then checksums
+// the 68 bytes holding it (gm/sendFrag.cc:147-155, :219-225; ib/sendFrag.cc:306-314).  Only the last four bytes of
+// that depend on the payload: the state after bytes [0, 64) -- the CRC register in the swapped domain, or the sum of
+// words 0..15 -- is the header's prefix, computed as soon as the descriptor is read (FragInfo::aux).
+constexpr uint32_t kSendHdrBytes = 72, kSendDataCsum = 64, kSendHdrCsum = 68;
+
+// The slice tables S_j[i] where a prefix is computed: the device image's (global, cache-resident; S_j[i] at
+// img[kImgSliceT + 4 i + j], as stage_slices reads them) or a workgroup's LDS copy (stage_slices: j * 256 + i).
+struct SliceGlobal {
+    guint *S;
+    __device__ uint32_t operator()(uint32_t j, uint32_t i) const { return S[4u * i + j]; }
+};
+struct SliceLds {
+    const uint32_t *S;
+    __device__ uint32_t operator()(uint32_t j, uint32_t i) const { return S[256u * j + i]; }
+};
+
+// The prefix of 16 header words: slicing-by-4 in the swapped domain (thread_crc's steps), or their sum.
+// (Four 16-byte quarters side by side joined by shifts -- four dependent rounds instead of sixteen -- measured
+// slower in the fused kernels: IB pairs 0.233 -> 0.333 ms, profiles/r07/send_pack_ab_chain4.txt.)
+template <class Tab>
+__device__ __forceinline__ uint32_t send_prefix_words(const uint32_t *w, bool crc, const Tab &tab) {
+    if (!crc) {
+        uint32_t sm = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sm += w[i];
+        return sm;
+    }
+    uint32_t C = __builtin_bswap32(kCrcInit);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const uint32_t X = C ^ w[i];
+        C = tab(0u, X & 255u) ^ tab(1u, (X >> 8) & 255u) ^ tab(2u, (X >> 16) & 255u) ^ tab(3u, X >> 24);
+    }
+    return C;
+}
+
+// ... of the header at h (4-byte aligned); mode NONE has none
+template <class Tab>
+__device__ __forceinline__ uint32_t send_hdr_prefix(const uint8_t *h, int mode, const Tab &tab) {
+    if (mode == LAMPI_CSUM_NONE) return 0u;
+    uint32_t w[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) w[i] = *(guint *)(h + 4 * i);
+    return send_prefix_words(w, mode == LAMPI_CSUM_CRC32, tab);
+}
+
+// The two words of one header (one thread per fragment; no tables): v = the fragment's bcopy_uicrc / bcopy_uicsum,
+// empty = a fragment of length 0, prefix = send_hdr_prefix of this header.
+//   GM  CRC / SUM: @64 = v, @68 = headerChecksum(H, 68, 18) with the word @68 taken as 0 (gm/sendFrag.cc:134):
+//                  bswap32(uicrc(H, 68)) / the sum of words 0..16;  NONE: nothing written
+//   IB  CRC / SUM: @64 = v, 0 when empty (ib/sendFrag.cc:306), @68 = uicrc(H, 68) unswapped / uicsum(H, 68);
+//                  NONE: both 0 (:313)
+// uicrc(H, 68) is the prefix register advanced over the four bytes of the word @64: thirty-two shift / xor steps
+// in the normal domain (polynomial 0x04C11DB7, MSB first).
+__device__ __forceinline__ void send_stamp(uint8_t *h, uint32_t v, bool empty, int kind, int mode, uint32_t prefix) {
+    gwuint *w64 = (gwuint *)(h + kSendDataCsum), *w68 = (gwuint *)(h + kSendHdrCsum);
+    if (mode == LAMPI_CSUM_NONE) {
+        if (kind == LAMPI_SEND_HDR_IB) {
+            *w64 = 0u;
+            *w68 = 0u;
+        }
+        return;
+    }
+    const uint32_t dc = kind == LAMPI_SEND_HDR_IB && empty ? 0u : v;
+    uint32_t hc;
+    if (mode == LAMPI_CSUM_CRC32) {
+        uint32_t N = __builtin_bswap32(prefix ^ dc);
+#pragma unroll
+        for (int k = 0; k < 32; ++k) N = (N << 1) ^ ((uint32_t)((int32_t)N >> 31) & cx::kPoly);
+        hc = kind == LAMPI_SEND_HDR_IB ? N : __builtin_bswap32(N);
+    } else {
+        hc = prefix + dc;
+    }
+    *w64 = dc;
+    *w68 = hc;
+}
+
+// The send step per descriptor: CopySource's fragment, its header's prefix preloaded (aux) the way RecvSource::get
+// preloads the expected value, and the stamp given inside emit by whichever wave or join thread ends the fragment --
+// no out[f] store, no value scratch, no second pass over the headers.
+struct SendSource {
+    static constexpr bool kCopy = true;
+    static constexpr bool kPhase = false;
+    const lampi_copy_desc *d;
+    uint8_t *hdrs;  // header f at hdrs + f * hdr_stride
+    size_t hdr_stride;
+    const uint32_t *img;
+    int kind, mode;
+    __device__ FragInfo get(size_t f) const {
+        const lampi_copy_desc x = d[f];
+        const uint32_t len = x.copylen > x.csumlen ? x.copylen : x.csumlen;
+        return {(gbyte *)(uintptr_t)x.src, len, x.partial, (uint8_t *)(uintptr_t)x.dst, x.copylen,
+                send_hdr_prefix(hdrs + f * hdr_stride, mode, SliceGlobal{(guint *)(img + kImgSliceT)})};
+    }
+    // the join kernels' descriptor read: every lane of a fragment's group reads it, only the one that emits needs
+    // the prefix, so stamp takes it then (FragInfo::lazy)
+    __device__ FragInfo get_join(size_t f) const {
+        const lampi_copy_desc x = d[f];
+        const uint32_t len = x.copylen > x.csumlen ? x.copylen : x.csumlen;
+        return {(gbyte *)(uintptr_t)x.src, len, x.partial, (uint8_t *)(uintptr_t)x.dst, x.copylen, 0u, 1u};
+    }
+    __device__ void stamp(size_t f, uint32_t v, const FragInfo &fi) const {
+        uint8_t *h = hdrs + f * hdr_stride;
+        const uint32_t prefix = fi.lazy ? send_hdr_prefix(h, mode, SliceGlobal{(guint *)(img + kImgSliceT)}) : fi.aux;
+        send_stamp(h, v, fi.len == 0u, kind, mode, prefix);
+    }
+};
+
+// ... with checksumming off (CopyOnlySource's plain copy): IB's two zeros, nothing for GM (hdrs may be null there)
+struct SendCopyOnlySource : SendSource {
+    __device__ FragInfo get(size_t f) const {
+        const lampi_copy_desc x = d[f];
+        return {(gbyte *)(uintptr_t)x.src, x.copylen, 0u, (uint8_t *)(uintptr_t)x.dst, x.copylen};
+    }
+    __device__ void stamp(size_t f, uint32_t, const FragInfo &) const {
+        if (kind == LAMPI_SEND_HDR_IB) send_stamp(hdrs + f * hdr_stride, 0u, true, kind, LAMPI_CSUM_NONE, 0u);
+    }
+};
+template <class S>
+struct IsSend : std::false_type {};
+template <>
+struct IsSend<SendSource> : std::true_type {};
+template <>
+struct IsSend<SendCopyOnlySource> : std::true_type {};
+// a fragment's descriptor as the join kernels read it
+template <class Src>
+__device__ __forceinline__ FragInfo join_get(const Src &src, size_t f) {
+    if constexpr (std::is_same<Src, SendSource>::value)
+        return src.get_join(f);
+    else
+        return src.get(f);
+}
+
 // The receive step's verdicts zeroed by the launch before the one that gives them (row groups: the first
 // launch, whose waves of group 0 zero the mask word of fragments f = 32i and f = 0 the count), instead of
 // a kernel of its own (zero_verdicts_kernel, ~5 us in the stream).
@@ -490,6 +628,10 @@ __device__ __forceinline__ void emit(const Src &src, Acc *out, size_t f, Acc v, 
     }
     if constexpr (IsSplit<Src>::value)
         if (fi.aux) return;  // the other launch's fragment
+    if constexpr (IsSend<Src>::value) {  // the send step: the header's two words instead of out[f]
+        src.stamp(f, (uint32_t)v, fi);
+        return;
+    }
     if constexpr (std::is_same<Src, RecvCopyOnlySource>::value) v = 0;  // no checksum with checksumming off
     out[f] = v;
     if constexpr (IsRecv<Src>::value) src.verdict(f, v, fi);
@@ -2958,7 +3100,7 @@ __global__ void __launch_bounds__(256) crc_light_group_join_kernel(const Src src
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, f = i / G;
     const uint32_t j = (uint32_t)(i & (G - 1u));
     if (f >= n) return;  // (the G lanes of a fragment leave or stay together)
-    const FragInfo fi = src.get(f);
+    const FragInfo fi = join_get(src, f);
     const uint32_t R = (uint32_t)(((uint64_t)fi.len + kRowBytes - 1) / kRowBytes);
     const uint32_t *p = groups + f * W;
     if (fi.len < 16u || R <= 1u) {  // (one group: its value as it is)
@@ -3878,7 +4020,7 @@ __global__ void __launch_bounds__(256) sum_group_join_kernel(const Src src, size
     uint32_t sm = 0;
     for (uint32_t g = j; g < W; g += G) sm += p[g];
     for (uint32_t o = G >> 1; o >= 1u; o >>= 1) sm += (uint32_t)__shfl_xor((int)sm, (int)o);
-    if (j == 0) emit(src, out, f, sm, src.get(f));
+    if (j == 0) emit(src, out, f, sm, join_get(src, f));
 }
 
 // Acc = uint32_t: uicsum (32-bit words); Acc = uint64_t: csum (64-bit words, ref
@@ -4221,6 +4363,65 @@ __global__ void __launch_bounds__(256) scatter_u32_kernel(const uint32_t *__rest
                                                           size_t stride) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) *(uint32_t *)(dst + (size_t)i * stride) = vals[i];
+}
+
+// lampi_send_hdr_fill as a kernel argument (the template as words)
+struct SendFill {
+    uint32_t tmpl[kSendHdrBytes / 4];
+    uint64_t frag_seq0, frag_seq_step, desc_ptr0, desc_ptr_stride, seq_offset0;
+};
+
+// The stamp after a batch whose checksums are in vals (the message form, whose fastest copy schedules have no single
+// owner of a fragment; the descriptor form's two-launch route): one thread per slot through send_stamp, the prefix
+// from a 4 KiB LDS copy of the slice tables as the header kernels (from the global tables every thread's sixteen
+// dependent gathers made this launch ~40 us for 16,384 slots, profiles/r07/send_pack_ab_chain16.txt, line B0).
+// kBuild (lampi_msg_send_pack): the thread first writes slot i's whole header -- fill.tmpl with dataLength @20,
+// frag_seq @32, sendFragDescPtr @48 and dataSeqOffset @56 of fragment i -- and takes the prefix from its registers;
+// with checksumming off GM keeps the template's word @64 and gets 0 @68 (gm/sendFrag.cc:134), IB two zeros.
+// Otherwise d[i] says whether fragment i is empty and the prefix is read from the header.
+template <bool kBuild>
+__global__ void __launch_bounds__(256) send_stamp_kernel(uint8_t *hdrs, size_t stride, uint32_t n,
+                                                         const uint32_t *__restrict__ vals,
+                                                         const lampi_copy_desc *__restrict__ d, const SendFill fill,
+                                                         size_t msg_len, size_t frag_len, int kind, int mode,
+                                                         const uint32_t *__restrict__ img) {
+    __shared__ uint32_t S[1024];
+    if (mode == LAMPI_CSUM_CRC32) stage_slices(S, img);
+    const SliceLds tab{S};
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint8_t *h = hdrs + (size_t)i * stride;
+    if constexpr (kBuild) {
+        const size_t off = (size_t)i * frag_len, rem = msg_len > off ? msg_len - off : 0;
+        const uint32_t len = (uint32_t)(rem < frag_len ? rem : frag_len);
+        uint32_t w[kSendHdrBytes / 4];
+#pragma unroll
+        for (int k = 0; k < (int)(kSendHdrBytes / 4); ++k) w[k] = fill.tmpl[k];
+        const uint64_t seq = fill.frag_seq0 + i * fill.frag_seq_step, ptr = fill.desc_ptr0 + i * fill.desc_ptr_stride,
+                       so = fill.seq_offset0 + (uint64_t)off;
+        w[5] = len;
+        w[8] = (uint32_t)seq;
+        w[9] = (uint32_t)(seq >> 32);
+        w[12] = (uint32_t)ptr;
+        w[13] = (uint32_t)(ptr >> 32);
+        w[14] = (uint32_t)so;
+        w[15] = (uint32_t)(so >> 32);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) *(gwuint *)(h + 4 * k) = w[k];
+        if (mode == LAMPI_CSUM_NONE) {
+            *(gwuint *)(h + kSendDataCsum) = kind == LAMPI_SEND_HDR_IB ? 0u : w[16];
+            *(gwuint *)(h + kSendHdrCsum) = 0u;
+            return;
+        }
+        send_stamp(h, vals[i], len == 0u, kind, mode, send_prefix_words(w, mode == LAMPI_CSUM_CRC32, tab));
+    } else {
+        if (mode == LAMPI_CSUM_NONE) {
+            send_stamp(h, 0u, true, kind, mode, 0u);
+            return;
+        }
+        const lampi_copy_desc x = d[i];
+        send_stamp(h, vals[i], (x.copylen | x.csumlen) == 0u, kind, mode, send_hdr_prefix(h, mode, tab));
+    }
 }
 
 // ---- chained checksums over typemap pieces ------------------------------------------------
@@ -4707,6 +4908,10 @@ struct ScratchTable {
     struct Slot {
         void *p = nullptr;
         size_t cap = 0;
+        // a second buffer for a batch's checksum words while the launchers that fill them use p (the send step's
+        // two-launch routes, stream_vals)
+        void *vals = nullptr;
+        size_t vals_cap = 0;
         // learned batch shapes, one record per (entry-point kind, descriptor array): a stream that
         // alternates batches from different arrays (GM's and IB's receive rings) keeps one shape each
         struct ShapeRec {
@@ -4744,6 +4949,10 @@ struct ScratchTable {
             (void)hipStreamSynchronize(it->first.second);
             (void)hipFree(it->second.p);
             g_scratch_bytes.fetch_sub((int64_t)it->second.cap, std::memory_order_relaxed);
+            if (it->second.vals) {
+                (void)hipFree(it->second.vals);
+                g_scratch_bytes.fetch_sub((int64_t)it->second.vals_cap, std::memory_order_relaxed);
+            }
             if (it->second.left) {
                 (void)hipFree(it->second.left);
                 g_scratch_bytes.fetch_sub(kLeftBytes, std::memory_order_relaxed);
@@ -4771,7 +4980,8 @@ ScratchTable::~ScratchTable() {
 }
 }  // namespace
 
-static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, bool *pooled) {
+// (vals: the slot's second buffer, at least 64 KiB, instead of its first, at least 1 MiB)
+static hipError_t stream_buffer(hipStream_t s, size_t bytes, void **out, bool *pooled, bool vals) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     hipError_t ce = hipStreamIsCapturing(s, &cs);
     if (ce != hipSuccess) return ce;
@@ -4781,29 +4991,41 @@ static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, bool *
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     ScratchTable::Slot &slot = t_scratch.slots[{dev, s}];
-    if (slot.cap < bytes) {
-        if (slot.p) {
+    void *&p = vals ? slot.vals : slot.p;
+    size_t &cap = vals ? slot.vals_cap : slot.cap;
+    if (cap < bytes) {
+        if (p) {
             e = hipStreamSynchronize(s);  // this thread's earlier launches on s still read the old buffer
-            if (e == hipSuccess) e = hipFree(slot.p);
+            if (e == hipSuccess) e = hipFree(p);
             if (e != hipSuccess) return e;  // the old buffer stays in the slot, still valid
-            g_scratch_bytes.fetch_sub((int64_t)slot.cap, std::memory_order_relaxed);
+            g_scratch_bytes.fetch_sub((int64_t)cap, std::memory_order_relaxed);
             // only the buffer goes: the learned shapes, the pair counters and their state are not tied to its
             // size (`slot = {}` here leaked the host-mapped shape records and the counters)
-            slot.p = nullptr;
-            slot.cap = 0;
+            p = nullptr;
+            cap = 0;
         }
-        const size_t want = std::max<size_t>(bytes + bytes / 4, 1u << 20);
-        e = hipMalloc(&slot.p, want);
+        const size_t want = std::max<size_t>(bytes + bytes / 4, vals ? 64u << 10 : 1u << 20);
+        e = hipMalloc(&p, want);
         if (e != hipSuccess) {
-            slot.p = nullptr;
-            slot.cap = 0;
+            p = nullptr;
+            cap = 0;
             return e;
         }
-        slot.cap = want;
+        cap = want;
         g_scratch_bytes.fetch_add((int64_t)want, std::memory_order_relaxed);
     }
-    *out = slot.p;
+    *out = p;
     return hipSuccess;
+}
+
+static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, bool *pooled) {
+    return stream_buffer(s, bytes, out, pooled, false);
+}
+
+// n checksum words that outlive the launchers filling them (which take stream_scratch themselves): the slot's
+// second buffer, pooled the same way -- no hipMallocAsync / hipFreeAsync pair in the stream.
+static hipError_t stream_vals(hipStream_t s, size_t n, uint32_t **out, bool *pooled) {
+    return stream_buffer(s, std::max<size_t>(n, 1) * sizeof(uint32_t), (void **)out, pooled, true);
 }
 
 // The pair kernel's leftover counters for stream s (this thread's): two, zeroed on the stream when created;
@@ -6164,6 +6386,100 @@ hipError_t launch_scatter_u32(const uint32_t *vals, size_t n, uint8_t *dst, size
     hipLaunchKernelGGL(scatter_u32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, vals, (uint32_t)n, dst,
                        stride);
     return hipGetLastError();
+}
+
+// The send step over descriptors (lampi_send_pack_batch): launch_bcopy_desc's dispatch of CopySource on SendSource,
+// whose emit stamps the header -- the table-light kernel one wave per fragment and the SUM workgroups / waves / row
+// groups (the join kernel's emit stamps); checksumming off: the plain copy schedules, IB's zeros from their emit.
+// Learned shapes are kept apart from the copy batches' (kinds 4 and 5).
+// Two CRC classes take two launches instead -- CopySource's kernels with the checksums in pooled scratch, then
+// send_stamp_kernel -- because the fused route measured slower there (profiles/r07/send_pack_ab_fused.txt, line B,
+// against profiles/r07/send_pack_ab.txt, line B; A = round 6's sequence of four entry points):
+//   batches the census saw as IB-sized (the pair kernel): with the stamp in its emit two header prefixes sit in
+//   every wave's prologue -- 262,144 x 1,976 bytes 0.2358 ms fused, 0.2060 ms in two launches (A 0.2266);
+//   row groups (GM's 65,456-byte payloads, learned or hinted): the join kernel's emitting lanes gather the prefix
+//   from the global tables -- 16,384 x 65,456 bytes 0.3999 ms fused, 0.3837 ms in two launches (A 0.3899).
+// A/B knob LAMPI_SEND_FUSED: 0 = every batch through launch_bcopy_desc into pooled scratch, then send_stamp_kernel
+// (the message form's route); 1 = every batch fused, the pair kernel and the CRC join too.
+hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, size_t hdr_stride, int kind, int mode,
+                            const uint32_t *img, hipStream_t s, uint32_t rows_hint) {
+    if (n == 0) return hipSuccess;
+    if (!img) return hipErrorInvalidValue;
+    static const int fused = [] {  // 0: two launches, 1: as measured, 2: fused everywhere
+        const char *e = LAMPI_AB_ENV("LAMPI_SEND_FUSED");
+        return !e ? 1 : e[0] == '0' ? 0 : 2;
+    }();
+    // batch(vals): a launch writing the n checksums to scratch; then the stamp
+    auto two_launches = [&](auto &&batch) {
+        uint32_t *vals = nullptr;
+        bool pooled = false;
+        hipError_t e = stream_vals(s, n, &vals, &pooled);
+        if (e != hipSuccess) return e;
+        e = batch(vals);
+        if (e == hipSuccess && !(mode == LAMPI_CSUM_NONE && kind == LAMPI_SEND_HDR_GM)) {
+            hipLaunchKernelGGL(send_stamp_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs,
+                               hdr_stride, (uint32_t)n, (const uint32_t *)vals, d, SendFill{}, (size_t)0, (size_t)0, kind,
+                               mode, img);
+            e = hipGetLastError();
+        }
+        return scratch_done(s, vals, pooled, e);
+    };
+    if (fused == 0)
+        return two_launches([&](uint32_t *vals) { return launch_bcopy_desc(d, n, vals, mode, img, s, rows_hint); });
+    bool pairs = false;
+    uint32_t *nhalf = nullptr;
+    if (mode == LAMPI_CSUM_NONE) {
+        SendCopyOnlySource co;
+        static_cast<SendSource &>(co) = SendSource{d, hdrs, hdr_stride, img, kind, mode};
+        rows_hint = learned_rows_hint(co, n, s, 5, rows_hint, &pairs, &nhalf, kShapeRowsSum);
+        return launch_sum_copy_groups(co, n, nullptr, s, rows_hint, pairs);
+    }
+    const bool crc = mode == LAMPI_CSUM_CRC32;
+    const SendSource src{d, hdrs, hdr_stride, img, kind, mode};
+    rows_hint = learned_rows_hint(src, n, s, 4, rows_hint, &pairs, &nhalf, crc ? kShapeRows : kShapeRowsSum);
+    if (crc && pairs && fused != 2)
+        return two_launches(
+            [&](uint32_t *vals) { return launch_crc_light_pair_copy(CopySource{d}, n, img, vals, s, nhalf); });
+    if (crc && fused != 2 && light_groups(n, rows_hint) > 1)
+        return two_launches(
+            [&](uint32_t *vals) { return launch_crc_light_frag_copy(CopySource{d}, n, img, vals, s, rows_hint); });
+    if (crc && pairs) return launch_crc_light_pair_copy(src, n, img, nullptr, s, nhalf);
+    if (crc) return launch_crc_light_frag_copy(src, n, img, nullptr, s, rows_hint);
+    return launch_sum_copy_groups(src, n, nullptr, s, rows_hint, pairs);  // (pairs: a wave per fragment)
+}
+
+// The send step over a message (lampi_msg_send_pack): launch_msg_bcopy unchanged -- every tuned message schedule,
+// several of which have no single owner of a fragment (sum_copy_row_kernel's atomic row sums, the two-pass CRC
+// copies, the sum_row4k rows) -- with the checksums in pooled scratch, then one send_stamp_kernel<true> that writes
+// the headers.  Checksumming off: the SUM copy schedules, their sums unused (as lampi_msg_bcopy_strided).
+hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
+                                size_t slot_stride, const lampi_send_hdr_fill &fill, size_t n, int kind, int mode,
+                                const uint32_t *img, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (!img) return hipErrorInvalidValue;
+    SendFill f;
+    static_assert(sizeof(f.tmpl) == sizeof(fill.tmpl), "header template");
+    std::memcpy(f.tmpl, fill.tmpl, sizeof(f.tmpl));
+    f.frag_seq0 = fill.frag_seq0;
+    f.frag_seq_step = fill.frag_seq_step;
+    f.desc_ptr0 = fill.desc_ptr0;
+    f.desc_ptr_stride = fill.desc_ptr_stride;
+    f.seq_offset0 = fill.seq_offset0;
+    uint32_t *vals = nullptr;
+    bool pooled = false;
+    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    if (e != hipSuccess) return e;
+    const bool none = mode == LAMPI_CSUM_NONE;
+    if (!(none && msg_len == 0))  // (nothing to copy, no checksum)
+        e = launch_msg_bcopy(base, msg_len, frag_len, kCrcInit, ring + kSendHdrBytes, slot_stride, n, vals,
+                             none ? LAMPI_CSUM_SUM32 : mode, img, s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(send_stamp_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ring, slot_stride,
+                           (uint32_t)n, (const uint32_t *)vals, (const lampi_copy_desc *)nullptr, f, msg_len, frag_len,
+                           kind, mode, img);
+        e = hipGetLastError();
+    }
+    return scratch_done(s, vals, pooled, e);
 }
 
 hipError_t launch_chain(const lampi_copy_desc *d, size_t npieces, const uint32_t *first, size_t nfrags, uint32_t *out,

@@ -57,6 +57,16 @@ hipError_t launch_crc_regular_copy(const uint8_t *base, size_t n, size_t frag_le
 // Fragments of a message, each copied to dst + k*dst_stride with its checksum fused.
 hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint8_t *dst,
                             size_t dst_stride, size_t n, uint32_t *out, int mode, const uint32_t *img, hipStream_t s);
+// The send step (ref src/path/gm/sendFrag.cc:143-226, src/path/ib/sendFrag.cc:119-138, :289-320): the copies of
+// launch_bcopy_desc with each 72-byte header's dataChecksum @64 and checksum @68 stamped by whoever finishes the
+// fragment (kind = lampi_send_hdr_kind, mode = lampi_csum_mode, NONE included; header f at hdrs + f*hdr_stride) ...
+hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, size_t hdr_stride, int kind, int mode,
+                            const uint32_t *img, hipStream_t s, uint32_t rows_hint = 1);
+// ... and of launch_msg_bcopy into ring + 72 + k*slot_stride, followed by one launch that builds slot k's whole
+// header from `fill` (host memory, read here) and stamps it.
+hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
+                                size_t slot_stride, const lampi_send_hdr_fill &fill, size_t n, int kind, int mode,
+                                const uint32_t *img, hipStream_t s);
 // RecvDesc_t::CopyToApp per descriptor (copy min(length, app_len), checksum length, verify).
 hipError_t launch_copy_to_app(const lampi_recv_desc *d, size_t n, const uint8_t *expected, size_t exp_stride,
                               int64_t *copied, uint32_t *csum, uint32_t *mask, uint32_t *nbad, int mode,

@@ -736,6 +736,51 @@ int lampi_msg_bcopy(const void *d_msg, size_t msg_len, size_t frag_len, void *d_
                                    stream);
 }
 
+// The send step in one call (ref src/path/gm/sendFrag.cc:143-226, src/path/ib/sendFrag.cc:119-138, :289-320):
+// no allocation, no scatter launch, the headers read once (frag_csum.hip: SendSource, launch_send_pack).
+int lampi_send_pack_batch(const lampi_copy_desc *d_descs, size_t n, void *d_hdrs, size_t hdr_stride, int hdr_kind,
+                          int mode, void *stream) {
+    const uint32_t rows_hint = std::max(1u, LAMPI_CSUM_ROWS_HINT_OF(mode));
+    const int base_mode = mode & ~LAMPI_CSUM_ROWS_HINT_MASK;
+    if (base_mode != LAMPI_CSUM_CRC32 && base_mode != LAMPI_CSUM_SUM32 && base_mode != LAMPI_CSUM_NONE)
+        return to_int(hipErrorInvalidValue);
+    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return to_int(hipErrorInvalidValue);
+    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < 72) return to_int(hipErrorInvalidValue);
+    // GM with checksumming off writes no header word (gm/sendFrag.cc:153-155, :219): the headers may be absent
+    const bool no_hdrs = base_mode == LAMPI_CSUM_NONE && hdr_kind == LAMPI_SEND_HDR_GM;
+    if (n == 0) return 0;
+    if (!d_descs || (!d_hdrs && !no_hdrs) || n > 0xFFFFFFFFull) return to_int(hipErrorInvalidValue);
+    int dev = 0;
+    hipError_t e = current_device(&dev);
+    if (e != hipSuccess) return to_int(e);
+    const uint32_t *img = nullptr;
+    e = device_tables(dev, &img);
+    if (e != hipSuccess) return to_int(e);
+    return to_int(launch_send_pack(d_descs, n, (uint8_t *)d_hdrs, hdr_stride, hdr_kind, base_mode, img,
+                                   (hipStream_t)stream, rows_hint));
+}
+
+int lampi_msg_send_pack(const void *d_msg, size_t msg_len, size_t frag_len, void *d_ring, size_t slot_stride,
+                        const lampi_send_hdr_fill *h_fill, int hdr_kind, int mode, void *stream) {
+    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
+        return to_int(hipErrorInvalidValue);
+    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return to_int(hipErrorInvalidValue);
+    if (frag_len == 0 || frag_len > 0xFFFFFFFFull || !d_ring || !h_fill || ((uintptr_t)d_ring & 7u) ||
+        (slot_stride & 7u) || slot_stride < 72 || slot_stride - 72 < frag_len || (msg_len && !d_msg))
+        return to_int(hipErrorInvalidValue);
+    // a zero-length message is one empty fragment (the path layer still sends a header)
+    const size_t n = msg_len ? (msg_len + frag_len - 1) / frag_len : 1;
+    if (n > 0xFFFFFFFFull) return to_int(hipErrorInvalidValue);
+    int dev = 0;
+    hipError_t e = current_device(&dev);
+    if (e != hipSuccess) return to_int(e);
+    const uint32_t *img = nullptr;
+    e = device_tables(dev, &img);
+    if (e != hipSuccess) return to_int(e);
+    return to_int(launch_msg_send_pack((const uint8_t *)d_msg, msg_len, frag_len, (uint8_t *)d_ring, slot_stride, *h_fill,
+                                       n, hdr_kind, mode, img, (hipStream_t)stream));
+}
+
 int lampi_chain_csum_batch_strided(const lampi_copy_desc *d_pieces, size_t npieces, const uint32_t *d_first,
                                    size_t nfrags, void *d_out, size_t out_stride, int mode, void *stream) {
     if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)

@@ -9,9 +9,10 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._lib import BY_BYTES, CRC32, CRC_INITIAL_REGISTER, NONE, SUM32, check, lib, rows_hint_bits
+from ._lib import (BY_BYTES, CRC32, CRC_INITIAL_REGISTER, HDR_GM, HDR_IB, NONE, SUM32, SendHdrFill, check, lib,
+                   rows_hint_bits)
 
-__all__ = ["CRC32", "SUM32", "NONE", "chain_copy_to_app_batch", "frag_bcopy_batch_strided", "msg_bcopy_strided",
+__all__ = ["CRC32", "SUM32", "NONE", "HDR_GM", "HDR_IB", "send_pack_batch", "msg_send_pack","chain_copy_to_app_batch", "frag_bcopy_batch_strided", "msg_bcopy_strided",
            "chain_csum_batch_strided", "header_csum_batch_strided", "frag_csum_batch", "diag_frag_csum_batch_per_wave", "frag_csum64_batch", "frag_bcopy_batch", "msg_bcopy", "msg_csum", "fill_stream", "fill_stream_frags",
            "make_descs", "make_copy_descs", "as_u32", "chain_csum_batch", "header_csum_batch", "header_check_batch", "check_data_batch",
            "mask_bits", "make_recv_descs", "copy_to_app_batch"]
@@ -260,6 +261,70 @@ def msg_bcopy_strided(msg: torch.Tensor, frag_len: int, dst: torch.Tensor, dst_s
     check(lib().lampi_msg_bcopy_strided(msg.data_ptr(), nbytes, frag_len, dst.data_ptr(), dst_stride,
                                         partial & 0xFFFFFFFF, ptr, out_stride, mode, _stream_handle(stream)),
           "lampi_msg_bcopy_strided")
+
+
+SEND_HDR_BYTES = 72  # gmHeaderData / ibDataHdr_t (dataChecksum @64, checksum @68)
+
+
+def send_pack_batch(descs: torch.Tensor, hdrs: torch.Tensor | None, hdr_stride: int, offset: int = 0,
+                    kind: int = HDR_GM, mode: int = CRC32, n: int | None = None,
+                    stream: torch.cuda.Stream | None = None, rows_hint: int = 0) -> torch.Tensor | None:
+    """The send step in one call (src/path/gm/sendFrag.cc:143-226, src/path/ib/sendFrag.cc:289-320): every
+    ``lampi_copy_desc`` copied with its checksum fused, and header i -- 72 bytes at byte offset + i*hdr_stride of
+    ``hdrs``, bytes [0, 64) already filled -- given dataChecksum @64 and the header checksum @68 of ``kind``
+    (HDR_GM / HDR_IB).  ``hdrs`` may be None only for HDR_GM with mode NONE; returns ``hdrs``."""
+    _require_cuda(descs, "descs")
+    count = descs.numel() * descs.element_size() // 32 if n is None else int(n)
+    if count * 32 > descs.numel() * descs.element_size():
+        raise ValueError("n exceeds the descriptor tensor")
+    ptr = None
+    if hdrs is None:
+        if not (kind == HDR_GM and mode == NONE):
+            raise ValueError("hdrs is required unless kind is HDR_GM and mode is NONE")
+    else:
+        _require_cuda(hdrs, "hdrs")
+        if count and offset + (count - 1) * hdr_stride + SEND_HDR_BYTES > hdrs.numel() * hdrs.element_size():
+            raise ValueError(f"hdrs is too small for {count} headers of stride {hdr_stride}")
+        ptr = hdrs.data_ptr() + offset
+    check(lib().lampi_send_pack_batch(descs.data_ptr(), count, ptr, hdr_stride, kind, mode | rows_hint_bits(rows_hint),
+                                      _stream_handle(stream)), "lampi_send_pack_batch")
+    return hdrs
+
+
+def msg_send_pack(msg: torch.Tensor, frag_len: int, ring: torch.Tensor, slot_stride: int, tmpl, frag_seq0: int = 0,
+                  frag_seq_step: int = 0, desc_ptr0: int = 0, desc_ptr_stride: int = 0, seq_offset0: int = 0,
+                  kind: int = HDR_GM, mode: int = CRC32, msg_len: int | None = None,
+                  stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """A device message made a wire-ready ring: fragment k copied to ``ring`` + k*slot_stride + 72 with its checksum
+    fused, and slot k's whole 72-byte header built on the device from ``tmpl`` (72 bytes; dataLength @20,
+    frag_seq @32 = frag_seq0 + k*frag_seq_step, sendFragDescPtr @48 = desc_ptr0 + k*desc_ptr_stride,
+    dataSeqOffset @56 = seq_offset0 + k*frag_len, then @64 / @68 of ``kind``).  Returns ``ring``."""
+    _require_cuda(msg, "msg")
+    _require_cuda(ring, "ring")
+    nbytes = msg.numel() * msg.element_size() if msg_len is None else int(msg_len)
+    if nbytes > msg.numel() * msg.element_size():
+        raise ValueError("msg_len exceeds the tensor")
+    if frag_len < 1 or slot_stride < SEND_HDR_BYTES + frag_len:
+        raise ValueError("slot_stride must hold the header and a whole fragment")
+    n = (nbytes + frag_len - 1) // frag_len if nbytes else 1
+    last = nbytes - (n - 1) * frag_len
+    if (n - 1) * slot_stride + SEND_HDR_BYTES + last > ring.numel() * ring.element_size():
+        raise ValueError("ring is too small")
+    t = np.ascontiguousarray(np.frombuffer(bytes(tmpl), dtype=np.uint8) if not isinstance(tmpl, np.ndarray)
+                             else tmpl.view(np.uint8).reshape(-1))
+    if t.size != SEND_HDR_BYTES:
+        raise ValueError("tmpl must be 72 bytes")
+    fill = SendHdrFill()
+    fill.tmpl[:] = t.tolist()
+    m64 = 2**64 - 1
+    fill.frag_seq0, fill.frag_seq_step = frag_seq0 & m64, frag_seq_step & m64
+    fill.desc_ptr0, fill.desc_ptr_stride = desc_ptr0 & m64, desc_ptr_stride & m64
+    fill.seq_offset0 = seq_offset0 & m64
+    import ctypes
+
+    check(lib().lampi_msg_send_pack(msg.data_ptr() if nbytes else None, nbytes, frag_len, ring.data_ptr(), slot_stride,
+                                    ctypes.addressof(fill), kind, mode, _stream_handle(stream)), "lampi_msg_send_pack")
+    return ring
 
 
 def chain_csum_batch(pieces: torch.Tensor, first, mode: int = CRC32, out: torch.Tensor | None = None,
