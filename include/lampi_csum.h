@@ -572,7 +572,9 @@ int lampi_fill_stream_frags(void *d_dst, size_t n, size_t frag_len, uint64_t see
 
 /* Release the calling thread's staging resources of the host entry points (streams, device
  * buffers, pinned bounce buffer) and its device scratch of the batched entry points.  They are also released automatically when the thread exits
- * or switches to another device; the next host call on the thread allocates them again. */
+ * or switches to another device; the next host call on the thread allocates them again.
+ * A device entry point called while its stream is being captured into a graph takes scratch that stays
+ * with the calling thread until this release: replay such a graph only before it. */
 void lampi_host_release(void);
 
 /* Bytes of page-locked host memory the library's host paths hold right now, over all threads

@@ -43,6 +43,7 @@
 #include <mutex>
 #include <type_traits>
 #include <utility>
+#include <vector>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -4881,8 +4882,12 @@ static dim3 grid_for(size_t n, uint32_t fpw) { return dim3((unsigned)((n + (size
 // launches on it are the only users of the old buffer), then frees it.  The thread's buffers are
 // freed at thread exit, by lampi_host_release() and, per stream, when the host pipeline destroys its
 // streams (release_stream_scratch); lampi_device_scratch_bytes() counts them for leak checks.
-// While s is being captured into a graph the graph gets its own allocation (hipMallocAsync; *pooled
-// set: release it with scratch_done), so no replay depends on a buffer a later call may replace.
+// While s is being captured into a graph the call gets a buffer of its own (hipMalloc with the thread's
+// capture mode relaxed, as torch's allocator does while capturing), so no replay depends on a buffer a later
+// call may replace; it is kept until the thread's scratch is released (thread exit, lampi_host_release()),
+// after which such a graph must not be replayed.  The graph's own allocations (hipMallocAsync /
+// hipFreeAsync nodes) did not hold on replays (tests/test_gpu_send_pack_graph.py): a memset node on such
+// memory took no effect after the first replay, and once a stamp read values its join had not yet written.
 namespace {
 std::atomic<int64_t> g_scratch_bytes{0};
 
@@ -4928,6 +4933,12 @@ struct ScratchTable {
         bool pair_broken = false;  // the counters could not be re-zeroed after a failed launch
     };
     std::map<std::pair<int, hipStream_t>, Slot> slots;
+    struct GraphBuf {
+        int dev;
+        void *p;
+        size_t bytes;
+    };
+    std::vector<GraphBuf> graph_bufs;  // the buffers of calls captured into graphs (stream_buffer)
     ScratchTable() = default;
     ScratchTable(const ScratchTable &) = delete;
     ScratchTable &operator=(const ScratchTable &) = delete;
@@ -4967,6 +4978,19 @@ struct ScratchTable {
         }
         if (have_cur && set != cur) (void)hipSetDevice(cur);
     }
+
+    void release_graph_bufs() {
+        int cur = -1;
+        const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+        int set = cur;
+        for (const GraphBuf &b : graph_bufs) {
+            if (b.dev != set && hipSetDevice(b.dev) == hipSuccess) set = b.dev;
+            (void)hipFree(b.p);  // (hipFree waits for the device's work)
+            g_scratch_bytes.fetch_sub((int64_t)b.bytes, std::memory_order_relaxed);
+        }
+        graph_bufs.clear();
+        if (have_cur && set != cur) (void)hipSetDevice(cur);
+    }
 };
 thread_local ScratchTable t_scratch;
 // Set once this thread's t_scratch has been destroyed.  Thread-local objects are destroyed in
@@ -4976,6 +5000,7 @@ thread_local ScratchTable t_scratch;
 thread_local bool t_scratch_dead = false;
 ScratchTable::~ScratchTable() {
     release_if([](const std::pair<int, hipStream_t> &) { return true; });
+    release_graph_bufs();
     t_scratch_dead = true;
 }
 }  // namespace
@@ -4985,11 +5010,23 @@ static hipError_t stream_buffer(hipStream_t s, size_t bytes, void **out, bool *p
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     hipError_t ce = hipStreamIsCapturing(s, &cs);
     if (ce != hipSuccess) return ce;
-    *pooled = cs != hipStreamCaptureStatusNone;
-    if (*pooled) return hipMallocAsync(out, bytes, s);
+    *pooled = false;  // (nothing for scratch_done to release: every buffer stays with the thread's table)
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
+    if (cs != hipStreamCaptureStatusNone) {
+        hipStreamCaptureMode m = hipStreamCaptureModeRelaxed;  // (hipMalloc is refused under the other modes)
+        e = hipThreadExchangeStreamCaptureMode(&m);
+        if (e != hipSuccess) return e;
+        void *gp = nullptr;
+        e = hipMalloc(&gp, std::max<size_t>(bytes, 4));
+        (void)hipThreadExchangeStreamCaptureMode(&m);
+        if (e != hipSuccess) return e;
+        t_scratch.graph_bufs.push_back({dev, gp, std::max<size_t>(bytes, 4)});
+        g_scratch_bytes.fetch_add((int64_t)std::max<size_t>(bytes, 4), std::memory_order_relaxed);
+        *out = gp;
+        return hipSuccess;
+    }
     ScratchTable::Slot &slot = t_scratch.slots[{dev, s}];
     void *&p = vals ? slot.vals : slot.p;
     size_t &cap = vals ? slot.vals_cap : slot.cap;
@@ -5084,6 +5121,7 @@ void release_stream_scratch(hipStream_t s) {
 void release_thread_scratch() {
     if (t_scratch_dead) return;
     t_scratch.release_if([](const std::pair<int, hipStream_t> &) { return true; });
+    t_scratch.release_graph_bufs();
 }
 
 int64_t device_scratch_bytes() { return g_scratch_bytes.load(std::memory_order_relaxed); }
@@ -6252,6 +6290,25 @@ static hipError_t launch_crc_light_copy(const uint8_t *base, size_t msg_len, siz
     return scratch_done(s, rows, pooled, e);
 }
 
+// out[0, n) = 0 on s before row sums add into it: hipMemsetAsync, except while s is being captured.  A memset
+// node did not hold on the replays after the first when out was the graph's own allocation (lampi_msg_send_pack's
+// values, before stream_buffer gave captured calls buffers of the thread's table) -- the sums came out added to
+// whatever the memory held (tests/test_gpu_send_pack_graph.py); a kernel node's stores are what every other value
+// of a captured call already relies on.
+__global__ void __launch_bounds__(256) zero_words_kernel(uint32_t *__restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = 0u;
+}
+
+static hipError_t zero_words(uint32_t *out, size_t n, hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(s, &cs);
+    if (e != hipSuccess) return e;
+    if (cs == hipStreamCaptureStatusNone) return hipMemsetAsync(out, 0, n * sizeof(uint32_t), s);
+    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint8_t *dst,
                             size_t dst_stride, size_t n, uint32_t *out, int mode, const uint32_t *img, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -6324,7 +6381,7 @@ hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len
         ((uintptr_t)base & 15u) == 0 && ((uintptr_t)dst & 3u) == 0 && dst_stride % 4 == 0 &&
         n * rpf <= 0xFFFFFFFFull) {
         if (rpf > 1) {  // rows add into out
-            const hipError_t e = hipMemsetAsync(out, 0, n * sizeof(uint32_t), s);
+            const hipError_t e = zero_words(out, n, s);
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL(sum_copy_row_kernel<>, dim3((unsigned)std::min<size_t>(n * rpf, kMaxWgGrid)), dim3(kSumRowThreads), 0, s,
@@ -6335,7 +6392,7 @@ hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len
     // shape, non-temporal stores): 4M x 4 KiB 69.8 -> 78.9% of read + write, GM 65,456-byte payloads
     // into 64 KiB slots at +72 61.6 -> 75.0% (profiles/r02_nt/)
     if (frag_len > kRowBytes && msg_len != 0) {  // fragments of several rows: row items (MsgRowCopySource)
-        const hipError_t e = hipMemsetAsync(out, 0, n * sizeof(uint32_t), s);
+        const hipError_t e = zero_words(out, n, s);
         if (e != hipSuccess) return e;
         launch_sum_copy(MsgRowCopySource{base, msg_len, frag_len, dst, dst_stride, (uint32_t)rpf}, n * rpf, out, s);
         return hipGetLastError();
