@@ -541,6 +541,62 @@ int lampi_copy_to_app_batch(const lampi_recv_desc *d_descs, size_t n, const void
                             size_t expected_stride, int64_t *d_copied, uint32_t *d_csum, uint32_t *d_mask,
                             uint32_t *d_nbad, int mode, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * The receive step in one call: header test, CopyToApp and CheckData.
+ *
+ * The mirror of the send step above, over the same 72-byte gmHeaderData / ibDataHdr_t (hdr_kind is
+ * enum lampi_send_hdr_kind).  The reference receives a fragment in one place: it tests the header
+ * (src/path/gm/path.cc:364-393, src/path/ib/path.cc:652-680); a fragment whose header fails goes back to the pool
+ * and never reaches the application (gm/path.cc:453-, ib/path.cc:702-717); otherwise RecvDesc_t::CopyToApp
+ * (src/path/common/BaseDesc.cc:288-342) copies it to the offset the header's dataSeqOffset gives
+ * (gm/recvFrag.h:83, ib/recvFrag.h:84) with the checksum fused (CopyFunction) and CheckData compares the result
+ * with the header's dataChecksum (gm/recvFrag.h:165-257, ib/recvFrag.cc:182-245).
+ *
+ * The header test, H = the 72 bytes:
+ *   LAMPI_SEND_HDR_GM  CRC32: uicrc(H, 72) == 0;  SUM32: the sum of words 0..17 == 2 x the word @68
+ *                      (lampi_header_check_batch with hdr_bytes 72, word_count 18, csum_offset 68)
+ *   LAMPI_SEND_HDR_IB  CRC32: the word @68 == uicrc(H, 68);  SUM32: == uicsum(H, 68), unswapped
+ *                      (lampi_header_compare_batch with crclen 68, csum_offset 68)
+ *   LAMPI_CSUM_NONE:   every header passes.
+ * Per fragment i:
+ *   header fails:  the fragment is dropped -- no payload byte is read, no application byte written;
+ *                  d_copied[i] = LAMPI_RECV_HDR_BAD, d_csum[i] = 0, bit i of d_hdr_mask set, d_nbad[0] counts it,
+ *                  its bit in d_data_mask clear;
+ *   header passes: exactly lampi_copy_to_app_batch's result with the expected value taken from the word @64:
+ *                  d_copied[i] = lengthToCopy, or LAMPI_RECV_DATA_BAD when the checksum differs (the bytes are
+ *                  delivered either way), d_csum[i] = the calculated value (0xFFFFFFFF / 0 when nothing is
+ *                  copied; 0 with LAMPI_CSUM_NONE), bit i of d_data_mask set when corrupt, d_nbad[1] counts it.
+ * Both masks (ceil(n/32) words each) and both counts are overwritten by the call.  Invalid arguments return
+ * hipErrorInvalidValue and write nothing.  No allocation in the stream: scratch comes from the stream's pooled
+ * buffers (inside a capture, from buffers the call owns, as the send step).
+ * ---------------------------------------------------------------------------------- */
+#define LAMPI_RECV_DATA_BAD (-1)   /* CopyToApp's own return for a corrupt payload */
+#define LAMPI_RECV_HDR_BAD  (-2)   /* header failed its test (or is malformed, ring form): fragment dropped */
+
+/* Descriptor form, the mirror of lampi_send_pack_batch.  Header i is the 72 bytes at (char *)d_hdrs + i*hdr_stride
+ * (d_hdrs and hdr_stride 4-byte aligned, hdr_stride >= 72); descriptor i is a lampi_recv_desc as for
+ * lampi_copy_to_app_batch.  mode takes LAMPI_CSUM_ROWS_HINT as lampi_copy_to_app_batch does (and the library learns
+ * the batches' shape the same way); LAMPI_CSUM_BY_BYTES is refused.  With LAMPI_CSUM_NONE no header is read and
+ * d_hdrs may be NULL.  n == 0 returns 0 with both counts zeroed; n < 2^32. */
+int lampi_recv_unpack_batch(const lampi_recv_desc *d_descs, size_t n, const void *d_hdrs, size_t hdr_stride,
+                            int hdr_kind, int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask,
+                            uint32_t *d_data_mask, uint32_t *d_nbad /* 2 words */, int mode, void *stream);
+
+/* Ring form, the mirror of lampi_msg_send_pack: no descriptors, every field is in the headers.  Slot k is the
+ * header at (char *)d_ring + k*slot_stride with its payload at +72 (d_ring and slot_stride 8-byte aligned,
+ * slot_stride >= 72); slots may arrive in any order.  length = dataLength @20 -- a header with dataLength >
+ * slot_stride - 72 is malformed and treated as a header failure in every mode, LAMPI_CSUM_NONE included (the
+ * reference trusts the field, gm/recvFrag.h:83; this library does not read past the slot); Offset =
+ * (dataSeqOffset @56 - seq_offset0) mod 2^64; destination d_app + Offset; AppBufferLen = app_len - Offset, or 0
+ * when Offset >= app_len (nothing copied, DataOK, BaseDesc.cc:312-316); then CopyToApp as above.  With
+ * LAMPI_CSUM_NONE nothing is tested but the length.  Outputs are indexed by slot.  Where the destinations of two
+ * slots overlap those bytes are unspecified; the verdicts stay per slot.  The schedule follows slot_stride
+ * (mode takes no hint bits).  nslots == 0 returns 0 with both counts zeroed; nslots < 2^32. */
+int lampi_msg_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride, int hdr_kind,
+                          void *d_app, size_t app_len, uint64_t seq_offset0,
+                          int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask, uint32_t *d_data_mask,
+                          uint32_t *d_nbad /* 2 words */, int mode, void *stream);
+
 /* RecvDesc_t::CopyToApp's non-contiguous branch on the device (ref src/path/common/BaseDesc.cc:326-340 --
  * non_contiguous_copy :72-163 and CheckData gm/recvFrag.h:213-257): lampi_chain_csum_batch's pieces and
  * fragments (the typemap pieces of each received fragment: src in the received payload, dst in the

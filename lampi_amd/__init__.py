@@ -10,8 +10,21 @@ kernels for gfx950 behind the C ABI in include/lampi_csum.h (liblampi_csum.so).
 * :mod:`lampi_amd.device` -- batched device-resident checksums over torch tensors
   (imported lazily: it needs torch).
 """
-from ._lib import CRC32, CRC_INITIAL_REGISTER, CRC_POLYNOMIAL, NONE, SUM32, FragDesc, lib  # noqa: F401
+from ._lib import (CRC32, CRC_INITIAL_REGISTER, CRC_POLYNOMIAL, NONE, RECV_DATA_BAD, RECV_HDR_BAD,  # noqa: F401
+                   SUM32, FragDesc, lib)
 from .memfunctions import (PartialState, PartialState64, bcopy_csum, bcopy_uicrc, bcopy_uicsum,  # noqa: F401
                            csum, header_checksum, uicrc, uicsum)
 
 __version__ = "0.1.0"
+
+# The receive step in one call lives in :mod:`lampi_amd.device`; the names resolve on first use, so importing the
+# package still needs no torch.
+_DEVICE_EXPORTS = ("recv_unpack_batch", "msg_recv_unpack")
+
+
+def __getattr__(name):
+    if name in _DEVICE_EXPORTS:
+        from . import device
+
+        return getattr(device, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -78,6 +78,8 @@ assert ctypes.sizeof(HostPiece) == 32
 
 HDR_GM = 0  # enum lampi_send_hdr_kind (include/lampi_csum.h)
 HDR_IB = 1
+RECV_DATA_BAD = -1  # LAMPI_RECV_DATA_BAD: CopyToApp's return for a corrupt payload
+RECV_HDR_BAD = -2  # LAMPI_RECV_HDR_BAD: the header failed its test (or is malformed), the fragment was dropped
 
 
 class SendHdrFill(ctypes.Structure):
@@ -128,6 +130,11 @@ PROTOTYPES = {
                                              c_void_p]),
     "lampi_msg_send_pack": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.c_int,
                                            ctypes.c_int, c_void_p]),
+    "lampi_recv_unpack_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_int, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int, c_void_p]),
+    "lampi_msg_recv_unpack": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, ctypes.c_int, c_void_p, c_size_t,
+                                             ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             ctypes.c_int, c_void_p]),
     "lampi_chain_csum_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
                                                       ctypes.c_int, c_void_p]),
     "lampi_header_csum_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, ctypes.c_uint32, ctypes.c_uint32,

@@ -128,6 +128,7 @@ struct FragInfo {
                        // latency hides under the fragment's rows (emit compares against it); send sources:
                        // the header's prefix (send_hdr_prefix)
     uint32_t lazy = 0;  // send sources in the join kernels: aux not computed, the emitting lane takes it
+                        // receive-step sources (RecvHdrBase): the header failed its test, the fragment is dropped
 };
 
 // ---- fragment sources (wave-uniform) ----------------------------------------------
@@ -523,6 +524,155 @@ __device__ __forceinline__ FragInfo join_get(const Src &src, size_t f) {
         return src.get(f);
 }
 
+// ---- the receive step in one call (lampi_recv_unpack_batch / lampi_msg_recv_unpack) ---------------------
+// The receiver tests a fragment's 72-byte header first (ref src/path/gm/path.cc:364-393, src/path/ib/path.cc:652-680);
+// a fragment whose header fails goes back to the pool and is never delivered (gm/path.cc:453-, ib/path.cc:702-717),
+// the others go through RecvDesc_t::CopyToApp (src/path/common/BaseDesc.cc:288-342) with the header's dataChecksum
+// (@64) as CheckData's expected value.  Here the test is part of the fragment's descriptor read: a dropped fragment
+// reads as len = copylen = 0 (FragInfo::lazy = 1 marks it), so no kernel issues a payload load or a store for it.
+//   GM  CRC: uicrc(H, 72) == 0;  SUM: the sum of words 0..17 == 2 x the word @68  (lampi_header_check_batch)
+//   IB  CRC: uicrc(H, 68) == the word @68, unswapped;  SUM: uicsum(H, 68) == it     (lampi_header_compare_batch)
+// The prefix of words 0..15 is the send step's (send_prefix_words); the register then advances over word 16 and,
+// for GM, word 17.
+constexpr uint32_t kRecvHdrWords = kSendHdrBytes / 4, kRecvLenWord = 5, kRecvSeqOffWord = 14;
+
+template <class Tab>
+__device__ __forceinline__ bool recv_hdr_ok(const uint32_t (&w)[kRecvHdrWords], int kind, int mode, const Tab &tab) {
+    if (mode == LAMPI_CSUM_NONE) return true;
+    const bool crc = mode == LAMPI_CSUM_CRC32;
+    uint32_t C = send_prefix_words(w, crc, tab);
+    if (!crc) {
+        const uint32_t s17 = C + w[16];  // uicsum(H, 68)
+        return kind == LAMPI_SEND_HDR_IB ? s17 == w[17] : s17 + w[17] == w[17] + w[17];
+    }
+    auto step = [&](uint32_t word) {
+        const uint32_t X = C ^ word;
+        C = tab(0u, X & 255u) ^ tab(1u, (X >> 8) & 255u) ^ tab(2u, (X >> 16) & 255u) ^ tab(3u, X >> 24);
+    };
+    step(w[16]);  // the register after 68 bytes, swapped domain: uicrc(H, 68) = bswap32(C)
+    if (kind == LAMPI_SEND_HDR_IB) return __builtin_bswap32(C) == w[17];
+    step(w[17]);
+    return C == 0u;
+}
+
+__device__ __forceinline__ void load_recv_hdr(const uint8_t *h, uint32_t (&w)[kRecvHdrWords]) {
+#pragma unroll
+    for (int i = 0; i < (int)kRecvHdrWords; ++i) w[i] = *(guint *)(h + 4 * i);
+}
+
+// What the pre-pass (recv_hdr_test_kernel) leaves per fragment for get(): the header's verdict and its dataChecksum.
+struct RecvHdrRec {
+    uint32_t ok, expected;
+};
+
+// What both forms share: where the headers are, how they are tested, and the verdict.
+struct RecvHdrBase {
+    static constexpr bool kCopy = true;
+    static constexpr bool kPhase = false;
+    const uint8_t *hdrs;     // header f at hdrs + f * hdr_stride (the ring form: the slots)
+    size_t hdr_stride;
+    const uint32_t *img;
+    int kind, mode;
+    const RecvHdrRec *rec;   // the pre-pass's records; nullptr: get() tests the header itself (global tables)
+    uint32_t empty;          // CopyFunction of 0 bytes: 0xFFFFFFFF (CRC) or 0 (SUM, NONE)
+    int64_t *copied;         // lengthToCopy, LAMPI_RECV_DATA_BAD or LAMPI_RECV_HDR_BAD
+    uint32_t *hmask, *dmask; // bit f set: header failed / payload corrupt
+    uint32_t *nbad;          // [0] headers, [1] payloads
+    // header f's verdict and expected value, from the record or from the header
+    __device__ bool header_ok(size_t f, uint32_t &expected) const {
+        if (rec) {
+            const RecvHdrRec r = rec[f];
+            expected = r.expected;
+            return r.ok != 0u;
+        }
+        uint32_t w[kRecvHdrWords];
+        load_recv_hdr(hdrs + f * hdr_stride, w);
+        expected = w[16];
+        return recv_hdr_ok(w, kind, mode, SliceGlobal{(guint *)(img + kImgSliceT)});
+    }
+    __device__ void verdict(size_t f, uint32_t v, const FragInfo &fi) const {
+        if (fi.lazy) {  // dropped: one atomic pair per bad header (rare)
+            copied[f] = (int64_t)LAMPI_RECV_HDR_BAD;
+            atomicOr(hmask + (f >> 5), 1u << (f & 31u));
+            atomicAdd(nbad, 1u);
+            return;
+        }
+        const uint32_t c = fi.copylen;
+        const bool bad = mode != LAMPI_CSUM_NONE && c != 0u && v != fi.aux;
+        copied[f] = bad ? (int64_t)LAMPI_RECV_DATA_BAD : (int64_t)c;
+        if (bad) {
+            atomicOr(dmask + (f >> 5), 1u << (f & 31u));
+            atomicAdd(nbad + 1, 1u);
+        }
+    }
+};
+
+// The descriptor form: RecvSource's fragment behind its header's test.
+struct RecvUnpackSource : RecvHdrBase {
+    const lampi_recv_desc *d;
+    __device__ FragInfo get(size_t f) const {
+        uint32_t e0 = 0u;
+        const bool ok = header_ok(f, e0);
+        const lampi_recv_desc x = d[f];
+        const uint32_t c = ok ? RecvSource::to_copy(x) : 0u;
+        return {(gbyte *)(uintptr_t)x.frag, c ? x.length : 0u, empty, (uint8_t *)(uintptr_t)x.app, c, c ? e0 : 0u,
+                ok ? 0u : 1u};
+    }
+};
+// ... with checksumming off: every header passes and none is read (hdrs may be null), RecvCopyOnlySource's copy
+struct RecvUnpackCopyOnlySource : RecvUnpackSource {
+    __device__ FragInfo get(size_t f) const {
+        const lampi_recv_desc x = d[f];
+        const uint32_t c = RecvSource::to_copy(x);
+        return {(gbyte *)(uintptr_t)x.frag, c, 0u, (uint8_t *)(uintptr_t)x.app, c, 0u};
+    }
+};
+
+// The ring form: the same FragInfo from the header alone (slot f = header + payload at +72).  length = dataLength
+// @20 -- a header claiming more than the slot holds is malformed and dropped like a failed one, in every mode --,
+// Offset = dataSeqOffset @56 - seq0 (mod 2^64, gm/recvFrag.h:83, ib/recvFrag.h:84), destination app + Offset,
+// AppBufferLen = app_len - Offset or 0 (BaseDesc.cc:307-316).  With checksumming off (mode NONE) only the length
+// is tested and lengthToCopy bytes are read.
+struct MsgRecvSource : RecvHdrBase {
+    uint8_t *app;
+    uint64_t app_len, seq0;
+    uint32_t max_len;  // slot_stride - 72
+    __device__ FragInfo get(size_t f) const {
+        const uint8_t *h = hdrs + f * hdr_stride;
+        uint32_t len, e0, so_lo, so_hi;
+        bool ok;
+        if (rec || mode == LAMPI_CSUM_NONE) {
+            len = *(guint *)(h + 4 * kRecvLenWord);
+            so_lo = *(guint *)(h + 4 * kRecvSeqOffWord);
+            so_hi = *(guint *)(h + 4 * kRecvSeqOffWord + 4);
+            e0 = 0u;
+            ok = rec ? header_ok(f, e0) : len <= max_len;  // (the pre-pass tested the length too)
+        } else {
+            uint32_t w[kRecvHdrWords];
+            load_recv_hdr(h, w);
+            len = w[kRecvLenWord];
+            so_lo = w[kRecvSeqOffWord];
+            so_hi = w[kRecvSeqOffWord + 1];
+            e0 = w[16];
+            ok = len <= max_len && recv_hdr_ok(w, kind, mode, SliceGlobal{(guint *)(img + kImgSliceT)});
+        }
+        const uint64_t off = (((uint64_t)so_hi << 32) | so_lo) - seq0;
+        const uint64_t room = off >= app_len ? 0u : app_len - off;
+        const uint32_t c = ok ? (uint32_t)min((uint64_t)len, room) : 0u;
+        const uint32_t n = mode == LAMPI_CSUM_NONE ? c : (c ? len : 0u);
+        return {(gbyte *)(h + kSendHdrBytes), n, empty, c ? app + off : app, c, c ? e0 : 0u, ok ? 0u : 1u};
+    }
+};
+
+template <class S>
+struct IsRecvHdr : std::is_base_of<RecvHdrBase, S> {};
+template <>
+struct IsRecv<RecvUnpackSource> : std::true_type {};
+template <>
+struct IsRecv<RecvUnpackCopyOnlySource> : std::true_type {};
+template <>
+struct IsRecv<MsgRecvSource> : std::true_type {};
+
 // The receive step's verdicts zeroed by the launch before the one that gives them (row groups: the first
 // launch, whose waves of group 0 zero the mask word of fragments f = 32i and f = 0 the count), instead of
 // a kernel of its own (zero_verdicts_kernel, ~5 us in the stream).
@@ -534,6 +684,20 @@ template <class S>
 struct IsGroupRecv : std::false_type {};
 template <>
 struct IsGroupRecv<GroupSource<RecvSource>> : std::true_type {};
+__device__ __forceinline__ void zero_verdict_words(const RecvHdrBase &src, size_t f) {
+    if ((f & 31u) == 0) {
+        src.hmask[f >> 5] = 0u;
+        src.dmask[f >> 5] = 0u;
+    }
+    if (f == 0) {
+        src.nbad[0] = 0u;
+        src.nbad[1] = 0u;
+    }
+}
+template <>
+struct IsGroupRecv<GroupSource<RecvUnpackSource>> : std::true_type {};
+template <>
+struct IsGroupRecv<GroupSource<MsgRecvSource>> : std::true_type {};
 
 // Byte-balanced descriptor batches (launch_crc_desc / launch_sum_desc for n <= kPlanMax): plan_kernel
 // cuts every fragment longer than the plan's window B into segments of at most B bytes and groups the
@@ -634,6 +798,8 @@ __device__ __forceinline__ void emit(const Src &src, Acc *out, size_t f, Acc v, 
         return;
     }
     if constexpr (std::is_same<Src, RecvCopyOnlySource>::value) v = 0;  // no checksum with checksumming off
+    if constexpr (IsRecvHdr<Src>::value)  // ... nor for a dropped fragment
+        if (fi.lazy || src.mode == LAMPI_CSUM_NONE) v = 0;
     out[f] = v;
     if constexpr (IsRecv<Src>::value) src.verdict(f, v, fi);
 }
@@ -5975,6 +6141,163 @@ hipError_t launch_copy_to_app(const lampi_recv_desc *d, size_t n, const uint8_t 
     if (crc && pairs) return launch_crc_light_pair_copy(src, n, img, csum, s, nhalf);
     if (crc) return launch_crc_light_frag_copy(src, n, img, csum, s, rows_hint);
     return launch_sum_copy_groups(src, n, csum, s, rows_hint, pairs);  // (pairs: a wave per fragment)
+}
+
+// ---- the receive step in one call ---------------------------------------------------------------------
+// Both masks and both counts, as zero_verdicts_kernel.
+__global__ void __launch_bounds__(256) zero_verdicts2_kernel(uint32_t *__restrict__ hmask, uint32_t *__restrict__ dmask,
+                                                             size_t nwords, uint32_t *__restrict__ nbad) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < nwords) {
+        hmask[i] = 0u;
+        dmask[i] = 0u;
+    }
+    if (i == 0) {
+        nbad[0] = 0u;
+        nbad[1] = 0u;
+    }
+}
+
+// The header tests as a pass of their own: one thread per header on a 4 KiB LDS copy of the slice tables (as
+// header_check_kernel), leaving {ok, dataChecksum} per fragment for the sources' get().  max_len: the ring form's
+// slot payload (a longer dataLength is malformed); 0xFFFFFFFF otherwise.
+__global__ void __launch_bounds__(256) recv_hdr_test_kernel(const uint8_t *__restrict__ hdrs, size_t stride, uint32_t n,
+                                                            int kind, int mode, uint32_t max_len,
+                                                            const uint32_t *__restrict__ img,
+                                                            RecvHdrRec *__restrict__ rec) {
+    __shared__ uint32_t S[1024];
+    if (mode == LAMPI_CSUM_CRC32) stage_slices(S, img);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t w[kRecvHdrWords];
+    load_recv_hdr(hdrs + (size_t)i * stride, w);
+    const bool ok = w[kRecvLenWord] <= max_len && recv_hdr_ok(w, kind, mode, SliceLds{S});
+    rec[i] = RecvHdrRec{ok ? 1u : 0u, w[16]};
+}
+
+// The schedules of launch_copy_to_app over a receive-step source (Src: RecvUnpackSource or MsgRecvSource, Co its twin
+// with checksumming off).  pairs: fragments of at most 2 KiB (CRC two to a wave, SUM / NONE one wave each).
+// Where the header is tested (profiles/r08/recv_unpack_ab.txt): inside get() -- the wave or
+// workgroup that owns the fragment -- except CRC pairs and the row groups of both modes, where every group's wave or
+// workgroup and every join lane would repeat the test ahead of its first payload load (CRC: sixteen dependent table
+// rounds; measured behind the three calls, GM CRC 0.4725 against 0.4167 ms, GM SUM 0.3823 against 0.3746 ms): there
+// one recv_hdr_test_kernel runs first and get() reads its record from the stream's second pooled buffer (GM CRC
+// 0.4148, GM SUM 0.3639 ms).  A/B knob LAMPI_RECV_PREPASS: 0 = never, 2 = always (SUM waves and the ring form with
+// checksumming off too).
+template <class Co, class Src>
+static hipError_t launch_recv_hdr(Src src, size_t n, uint32_t *csum, const uint32_t *img, hipStream_t s,
+                                  uint32_t rows_hint, bool pairs, uint32_t *nhalf, uint32_t max_len) {
+    static const int prepass = [] {
+        const char *e = LAMPI_AB_ENV("LAMPI_RECV_PREPASS");
+        return !e ? 1 : e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
+    }();
+    const int mode = src.mode;
+    const bool crc = mode == LAMPI_CSUM_CRC32, none = mode == LAMPI_CSUM_NONE;
+    const size_t nwords = (n + 31) / 32;
+    // row groups: the first launch zeroes the verdicts (zero_verdict_words), the join gives them; otherwise the
+    // fragments' own waves give them, after this
+    const bool groups = none  ? IsGroupRecv<GroupSource<Co>>::value && sum_groups(n, rows_hint) > 1
+                        : crc ? !pairs && light_groups(n, rows_hint) > 1
+                              : sum_groups(n, rows_hint) > 1;
+    if (!groups) {
+        hipLaunchKernelGGL(zero_verdicts2_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, src.hmask,
+                           src.dmask, nwords, src.nbad);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    // (checksumming off: the descriptor form reads no header; the ring form tests the length alone, in get())
+    const bool ring = max_len != 0xFFFFFFFFu;
+    const bool pre = prepass == 2 ? !none || ring : prepass == 1 && !none && (groups || (crc && pairs));
+    RecvHdrRec *rec = nullptr;
+    bool pooled = false;
+    if (pre) {
+        hipError_t e = stream_vals(s, 2 * n, (uint32_t **)&rec, &pooled);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(recv_hdr_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.hdrs,
+                           src.hdr_stride, (uint32_t)n, src.kind, mode, max_len, img, rec);
+        e = hipGetLastError();
+        if (e != hipSuccess) return scratch_done(s, rec, pooled, e);
+        src.rec = rec;
+    }
+    hipError_t e;
+    if (none) {  // copy only, every fragment DataOK: the SUM copy schedules without the sums
+        Co co;
+        static_cast<Src &>(co) = src;
+        e = launch_sum_copy_groups(co, n, csum, s, rows_hint, pairs);
+    } else if (crc && pairs) {
+        e = launch_crc_light_pair_copy(src, n, img, csum, s, nhalf);
+    } else if (crc) {
+        e = launch_crc_light_frag_copy(src, n, img, csum, s, rows_hint);
+    } else {
+        e = launch_sum_copy_groups(src, n, csum, s, rows_hint, pairs);  // (pairs: a wave per fragment)
+    }
+    return pre ? scratch_done(s, rec, pooled, e) : e;
+}
+
+static void fill_recv_hdr_base(RecvHdrBase &b, const uint8_t *hdrs, size_t hdr_stride, int kind, int mode,
+                               const uint32_t *img, int64_t *copied, uint32_t *hmask, uint32_t *dmask, uint32_t *nbad) {
+    b.hdrs = hdrs;
+    b.hdr_stride = hdr_stride;
+    b.img = img;
+    b.kind = kind;
+    b.mode = mode;
+    b.rec = nullptr;
+    b.empty = mode == LAMPI_CSUM_CRC32 ? 0xFFFFFFFFu : 0u;
+    b.copied = copied;
+    b.hmask = hmask;
+    b.dmask = dmask;
+    b.nbad = nbad;
+}
+
+// The descriptor form.  The batch's shape is learned as launch_copy_to_app learns it -- the census reads the
+// descriptors through RecvSource, whatever the headers say -- in records of its own (kinds 6 and 7).
+hipError_t launch_recv_unpack(const lampi_recv_desc *d, size_t n, const uint8_t *hdrs, size_t hdr_stride, int kind,
+                              int64_t *copied, uint32_t *csum, uint32_t *hmask, uint32_t *dmask, uint32_t *nbad, int mode,
+                              const uint32_t *img, hipStream_t s, uint32_t rows_hint) {
+    if (n == 0) return hipMemsetAsync(nbad, 0, 2 * sizeof(uint32_t), s);
+    if (!img) return hipErrorInvalidValue;
+    RecvUnpackSource src;
+    fill_recv_hdr_base(src, hdrs, hdr_stride, kind, mode, img, copied, hmask, dmask, nbad);
+    src.d = d;
+    bool pairs = false;
+    uint32_t *nhalf = nullptr;
+    if (mode == LAMPI_CSUM_NONE) {
+        RecvCopyOnlySource shape;
+        static_cast<RecvSource &>(shape) = RecvSource{d, 0u, nullptr, 0, copied, dmask, nbad};
+        rows_hint = learned_rows_hint(shape, n, s, 7, rows_hint, &pairs, &nhalf, kShapeRowsSum);
+    } else {
+        const bool crc = mode == LAMPI_CSUM_CRC32;
+        const RecvSource shape{d, src.empty, hdrs + kSendDataCsum, hdr_stride, copied, dmask, nbad};
+        rows_hint = learned_rows_hint(shape, n, s, 6, rows_hint, &pairs, &nhalf, crc ? kShapeRows : kShapeRowsSum);
+    }
+    return launch_recv_hdr<RecvUnpackCopyOnlySource>(src, n, csum, img, s, rows_hint, pairs, nhalf, 0xFFFFFFFFu);
+}
+
+// The ring form: nothing to learn, the slot size says what the fragments can be -- at most 2 KiB: pairs; otherwise
+// the slot's rows as the hint where a learned hint would be taken (kShapeRows / kShapeRowsSum rows or more).
+// MsgRecvSource is its own twin with checksumming off (get() reads the mode: the length still has to be tested).
+hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slot_stride, int kind, uint8_t *app,
+                                  size_t app_len, uint64_t seq0, int64_t *copied, uint32_t *csum, uint32_t *hmask,
+                                  uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s) {
+    if (nslots == 0) return hipMemsetAsync(nbad, 0, 2 * sizeof(uint32_t), s);
+    if (!img) return hipErrorInvalidValue;
+    MsgRecvSource src;
+    fill_recv_hdr_base(src, ring, slot_stride, kind, mode, img, copied, hmask, dmask, nbad);
+    src.app = app;
+    src.app_len = app_len;
+    src.seq0 = seq0;
+    const size_t room = std::min<size_t>(slot_stride - kSendHdrBytes, 0xFFFFFFFEull);
+    src.max_len = (uint32_t)room;
+    const bool crc = mode == LAMPI_CSUM_CRC32;
+    bool pairs = room <= (size_t)kRowBytes / 2;
+    if (pairs && crc) {  // (the pair kernel's leftover counters: not inside a capture, not on a stream that lost them)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone || !pair_counters_ok(s))
+            pairs = false;
+    }
+    const size_t R = (room + kRowBytes - 1) / kRowBytes;
+    const uint32_t rows_hint = R >= (crc ? kShapeRows : kShapeRowsSum) ? (uint32_t)std::min<size_t>(R, 4095) : 1u;
+    return launch_recv_hdr<MsgRecvSource>(src, nslots, csum, img, s, rows_hint, pairs, nullptr, src.max_len);
 }
 
 hipError_t launch_sum64_desc(const lampi_frag_desc *d, size_t n, uint64_t *out, bool phased, hipStream_t s) {

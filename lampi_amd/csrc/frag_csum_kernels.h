@@ -71,6 +71,18 @@ hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag
 hipError_t launch_copy_to_app(const lampi_recv_desc *d, size_t n, const uint8_t *expected, size_t exp_stride,
                               int64_t *copied, uint32_t *csum, uint32_t *mask, uint32_t *nbad, int mode,
                               const uint32_t *img, hipStream_t s, uint32_t rows_hint = 1);
+// The receive step in one call (ref src/path/gm/path.cc:364-393, src/path/ib/path.cc:652-680, then CopyToApp): the
+// schedules of launch_copy_to_app behind each 72-byte header's test (kind = lampi_send_hdr_kind); a fragment whose
+// header fails is dropped -- copied[f] = LAMPI_RECV_HDR_BAD, its bit in hmask, nbad[0] -- and the others are verified
+// against the header's dataChecksum @64 (dmask, nbad[1]).  Header f at hdrs + f*hdr_stride ...
+hipError_t launch_recv_unpack(const lampi_recv_desc *d, size_t n, const uint8_t *hdrs, size_t hdr_stride, int kind,
+                              int64_t *copied, uint32_t *csum, uint32_t *hmask, uint32_t *dmask, uint32_t *nbad, int mode,
+                              const uint32_t *img, hipStream_t s, uint32_t rows_hint = 1);
+// ... and with every field taken from the headers of a ring of header + payload slots: dataLength @20 (at most
+// slot_stride - 72), destination app + (dataSeqOffset @56 - seq0), room app_len less that offset.
+hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slot_stride, int kind, uint8_t *app,
+                                  size_t app_len, uint64_t seq0, int64_t *copied, uint32_t *csum, uint32_t *hmask,
+                                  uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s);
 // headerChecksum per header / receiver header check / CheckData (mask bit set = corrupt).
 hipError_t launch_header_csum(const uint8_t *hdrs, size_t n, size_t stride, uint32_t crclen, uint32_t word_count,
                               int mode, const uint32_t *img, uint8_t *out, size_t out_stride, hipStream_t s);

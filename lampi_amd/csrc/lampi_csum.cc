@@ -690,6 +690,55 @@ int lampi_copy_to_app_batch(const lampi_recv_desc *d_descs, size_t n, const void
                                      d_nbad, mode, img, (hipStream_t)stream, rows_hint));
 }
 
+// The receive step in one call (ref src/path/gm/path.cc:364-393, src/path/ib/path.cc:652-680, then
+// src/path/common/BaseDesc.cc:288-342): the header test, the drop of a fragment whose header failed, CopyToApp and
+// CheckData in the passes lampi_copy_to_app_batch makes (frag_csum.hip: RecvUnpackSource, launch_recv_unpack).
+int lampi_recv_unpack_batch(const lampi_recv_desc *d_descs, size_t n, const void *d_hdrs, size_t hdr_stride,
+                            int hdr_kind, int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask,
+                            uint32_t *d_data_mask, uint32_t *d_nbad, int mode, void *stream) {
+    const uint32_t rows_hint = std::max(1u, LAMPI_CSUM_ROWS_HINT_OF(mode));
+    mode &= ~LAMPI_CSUM_ROWS_HINT_MASK;  // (LAMPI_CSUM_BY_BYTES stays in and is refused)
+    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
+        return to_int(hipErrorInvalidValue);
+    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return to_int(hipErrorInvalidValue);
+    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < 72) return to_int(hipErrorInvalidValue);
+    const bool check = mode != LAMPI_CSUM_NONE;  // (checksumming off: no header is read)
+    if (!d_nbad || n > 0xFFFFFFFFull ||
+        (n && (!d_descs || (check && !d_hdrs) || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask)))
+        return to_int(hipErrorInvalidValue);
+    int dev = 0;
+    hipError_t e = current_device(&dev);
+    if (e != hipSuccess) return to_int(e);
+    const uint32_t *img = nullptr;
+    e = device_tables(dev, &img);
+    if (e != hipSuccess) return to_int(e);
+    return to_int(launch_recv_unpack(d_descs, n, check ? (const uint8_t *)d_hdrs : nullptr, hdr_stride, hdr_kind,
+                                     d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode, img, (hipStream_t)stream,
+                                     rows_hint));
+}
+
+// ... over a ring of header + payload slots, every field from the headers (MsgRecvSource, launch_msg_recv_unpack)
+int lampi_msg_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride, int hdr_kind, void *d_app,
+                          size_t app_len, uint64_t seq_offset0, int64_t *d_copied, uint32_t *d_csum,
+                          uint32_t *d_hdr_mask, uint32_t *d_data_mask, uint32_t *d_nbad, int mode, void *stream) {
+    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
+        return to_int(hipErrorInvalidValue);  // (no hint bits: the slot size says the shape)
+    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return to_int(hipErrorInvalidValue);
+    if (((uintptr_t)d_ring & 7u) || (slot_stride & 7u) || slot_stride < 72) return to_int(hipErrorInvalidValue);
+    if (!d_nbad || nslots > 0xFFFFFFFFull || (app_len && !d_app) ||
+        (nslots && (!d_ring || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask)))
+        return to_int(hipErrorInvalidValue);
+    int dev = 0;
+    hipError_t e = current_device(&dev);
+    if (e != hipSuccess) return to_int(e);
+    const uint32_t *img = nullptr;
+    e = device_tables(dev, &img);
+    if (e != hipSuccess) return to_int(e);
+    return to_int(launch_msg_recv_unpack((const uint8_t *)d_ring, nslots, slot_stride, hdr_kind, (uint8_t *)d_app,
+                                         app_len, seq_offset0, d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode,
+                                         img, (hipStream_t)stream));
+}
+
 int lampi_msg_csum(const void *d_msg, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *d_out, int mode,
                    void *stream) {
     if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32) return to_int(hipErrorInvalidValue);

@@ -9,10 +9,11 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._lib import (BY_BYTES, CRC32, CRC_INITIAL_REGISTER, HDR_GM, HDR_IB, NONE, SUM32, SendHdrFill, check, lib,
-                   rows_hint_bits)
+from ._lib import (BY_BYTES, CRC32, CRC_INITIAL_REGISTER, HDR_GM, HDR_IB, NONE, RECV_DATA_BAD, RECV_HDR_BAD, SUM32,
+                   SendHdrFill, check, lib, rows_hint_bits)
 
-__all__ = ["CRC32", "SUM32", "NONE", "HDR_GM", "HDR_IB", "send_pack_batch", "msg_send_pack","chain_copy_to_app_batch", "frag_bcopy_batch_strided", "msg_bcopy_strided",
+__all__ = ["CRC32", "SUM32", "NONE", "HDR_GM", "HDR_IB", "RECV_DATA_BAD", "RECV_HDR_BAD", "recv_unpack_batch", "msg_recv_unpack",
+           "send_pack_batch", "msg_send_pack","chain_copy_to_app_batch", "frag_bcopy_batch_strided", "msg_bcopy_strided",
            "chain_csum_batch_strided", "header_csum_batch_strided", "frag_csum_batch", "diag_frag_csum_batch_per_wave", "frag_csum64_batch", "frag_bcopy_batch", "msg_bcopy", "msg_csum", "fill_stream", "fill_stream_frags",
            "make_descs", "make_copy_descs", "as_u32", "chain_csum_batch", "header_csum_batch", "header_check_batch", "check_data_batch",
            "mask_bits", "make_recv_descs", "copy_to_app_batch"]
@@ -529,6 +530,73 @@ def copy_to_app_batch(descs: torch.Tensor, expected: torch.Tensor, expected_stri
                                         mode | rows_hint_bits(rows_hint), _stream_handle(stream)),
           "lampi_copy_to_app_batch")
     return copied[:count], csum[:count], mask, nbad
+
+
+def _unpack_out(count: int, device):
+    """(copied, csum, hdr_mask, data_mask, nbad[2]) for ``count`` fragments; the call overwrites all of them."""
+    words = max(1, (count + 31) // 32)
+    make = torch.zeros if count == 0 else torch.empty  # (an empty batch zeroes the counts only)
+    return (torch.empty(max(count, 1), dtype=torch.int64, device=device),
+            torch.empty(max(count, 1), dtype=torch.int32, device=device),
+            make(words, dtype=torch.int32, device=device), make(words, dtype=torch.int32, device=device),
+            torch.empty(2, dtype=torch.int32, device=device))
+
+
+def recv_unpack_batch(descs: torch.Tensor, hdrs: torch.Tensor | None, hdr_stride: int, offset: int = 0,
+                      kind: int = HDR_GM, mode: int = CRC32, rows_hint: int = 0, stream: torch.cuda.Stream | None = None,
+                      n: int | None = None):
+    """The receive step in one call (src/path/gm/path.cc:364-393, src/path/ib/path.cc:652-680, then
+    src/path/common/BaseDesc.cc:288-342): header i -- 72 bytes at byte offset + i*hdr_stride of ``hdrs`` -- is
+    tested as ``kind`` (HDR_GM / HDR_IB) says; a fragment whose header fails is dropped (copied RECV_HDR_BAD, nothing
+    read or delivered), the others go through CopyToApp against the header's dataChecksum @64 (copied = bytes
+    delivered, or RECV_DATA_BAD).  Returns (copied int64[n], csum int32[n], hdr_mask, data_mask, nbad int32[2] --
+    bad headers, corrupt payloads).  ``hdrs`` may be None with mode NONE (no header is read)."""
+    _require_cuda(descs, "descs")
+    count = descs.numel() * descs.element_size() // 32 if n is None else int(n)
+    if count * 32 > descs.numel() * descs.element_size():
+        raise ValueError("n exceeds the descriptor tensor")
+    ptr = None
+    if hdrs is None:
+        if (mode & 0xFF) != NONE:
+            raise ValueError("hdrs is required unless mode is NONE (checksumming off)")
+    else:
+        _require_cuda(hdrs, "hdrs")
+        if count and offset + (count - 1) * hdr_stride + SEND_HDR_BYTES > hdrs.numel() * hdrs.element_size():
+            raise ValueError(f"hdrs is too small for {count} headers of stride {hdr_stride}")
+        ptr = hdrs.data_ptr() + offset
+    copied, csum, hmask, dmask, nbad = _unpack_out(count, descs.device)
+    check(lib().lampi_recv_unpack_batch(descs.data_ptr(), count, ptr, hdr_stride, kind, copied.data_ptr(),
+                                        csum.data_ptr(), hmask.data_ptr(), dmask.data_ptr(), nbad.data_ptr(),
+                                        mode | rows_hint_bits(rows_hint), _stream_handle(stream)),
+          "lampi_recv_unpack_batch")
+    return copied[:count], csum[:count], hmask, dmask, nbad
+
+
+def msg_recv_unpack(ring: torch.Tensor, nslots: int, slot_stride: int, app: torch.Tensor, kind: int = HDR_GM,
+                    mode: int = CRC32, seq_offset0: int = 0, app_len: int | None = None,
+                    stream: torch.cuda.Stream | None = None):
+    """The receive step over a ring of header + payload slots, no descriptors (the mirror of msg_send_pack): slot k
+    = the 72-byte header at ``ring`` + k*slot_stride and its payload at +72, in any order; its length is the
+    header's dataLength @20 (more than slot_stride - 72: malformed, dropped like a failed header), its destination
+    ``app`` + (dataSeqOffset @56 - seq_offset0 mod 2^64), cut at ``app_len`` (default: the whole tensor).  Returns
+    (copied, csum, hdr_mask, data_mask, nbad) as recv_unpack_batch, indexed by slot."""
+    _require_cuda(ring, "ring")
+    _require_cuda(app, "app")
+    count = int(nslots)
+    if count < 0 or slot_stride < SEND_HDR_BYTES:
+        raise ValueError("slot_stride must hold the header")
+    if count * slot_stride > ring.numel() * ring.element_size():
+        raise ValueError("ring is too small (every slot may be read whole)")
+    room = app.numel() * app.element_size()
+    alen = room if app_len is None else int(app_len)
+    if not 0 <= alen <= room:
+        raise ValueError("app_len exceeds the tensor")
+    copied, csum, hmask, dmask, nbad = _unpack_out(count, ring.device)
+    check(lib().lampi_msg_recv_unpack(ring.data_ptr(), count, slot_stride, kind, app.data_ptr(), alen,
+                                      seq_offset0 & (2**64 - 1), copied.data_ptr(), csum.data_ptr(), hmask.data_ptr(),
+                                      dmask.data_ptr(), nbad.data_ptr(), mode, _stream_handle(stream)),
+          "lampi_msg_recv_unpack")
+    return copied[:count], csum[:count], hmask, dmask, nbad
 
 
 def mask_bits(mask: torch.Tensor, n: int) -> np.ndarray:
