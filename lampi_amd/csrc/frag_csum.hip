@@ -65,12 +65,21 @@
 
 namespace lampi {
 
+// A knob's value from the string LAMPI_AB_ENV gave for it (null: the measured default).  Each reader keeps the
+// macro with the literal name at its own site: that is what keeps the name out of the default library.
+static bool knob_on(const char *e) { return !(e && e[0] == '0'); }  // on unless "0"
+static uint32_t knob_u32(const char *e, uint32_t dflt) { return e ? (uint32_t)std::atoi(e) : dflt; }
+static size_t knob_size(const char *e, size_t dflt) { return e ? (size_t)std::atoll(e) : dflt; }
+// waves per workgroup: "16", "8" or "4"
+static int knob_waves(const char *e, int dflt) {
+    return !e ? dflt : e[0] == '1' ? 16 : e[0] == '8' ? 8 : e[0] == '4' ? 4 : dflt;
+}
+
 // per-stream device scratch (defined with the launchers)
 static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, bool *pooled);
 static hipError_t scratch_done(hipStream_t s, void *p, bool pooled, hipError_t e);
 static hipError_t pair_counters(hipStream_t s, uint32_t **cur, uint32_t **next);
 static void reset_pair_counters(hipStream_t s);
-static hipError_t scratch_done(hipStream_t s, void *p, bool pooled, hipError_t e);
 
 namespace {
 
@@ -381,13 +390,6 @@ struct IsSparse : std::false_type {};
 template <>
 struct IsSparse<SparseDescSource> : std::true_type {};
 
-template <class S>
-struct IsRecv : std::false_type {};
-template <>
-struct IsRecv<RecvSource> : std::true_type {};
-template <>
-struct IsRecv<RecvCopyOnlySource> : std::true_type {};
-
 // ---- the send step's header stamp (lampi_send_pack_batch / lampi_msg_send_pack) ------------------------
 // The 72-byte data header of gmHeaderData / ibDataHdr_t (ref src/path/gm/header.h:56-70, src/path/ib/header.h:48-62):
 // dataChecksum @64, checksum @68.  The reference stores the fused copy's value v in dataChecksum and then checksums
@@ -510,11 +512,7 @@ struct SendCopyOnlySource : SendSource {
     }
 };
 template <class S>
-struct IsSend : std::false_type {};
-template <>
-struct IsSend<SendSource> : std::true_type {};
-template <>
-struct IsSend<SendCopyOnlySource> : std::true_type {};
+struct IsSend : std::is_base_of<SendSource, S> {};
 // a fragment's descriptor as the join kernels read it
 template <class Src>
 __device__ __forceinline__ FragInfo join_get(const Src &src, size_t f) {
@@ -666,12 +664,9 @@ struct MsgRecvSource : RecvHdrBase {
 
 template <class S>
 struct IsRecvHdr : std::is_base_of<RecvHdrBase, S> {};
-template <>
-struct IsRecv<RecvUnpackSource> : std::true_type {};
-template <>
-struct IsRecv<RecvUnpackCopyOnlySource> : std::true_type {};
-template <>
-struct IsRecv<MsgRecvSource> : std::true_type {};
+// every receive source: emit asks it for the fragment's verdict
+template <class S>
+struct IsRecv : std::integral_constant<bool, std::is_base_of<RecvSource, S>::value || IsRecvHdr<S>::value> {};
 
 // The receive step's verdicts zeroed by the launch before the one that gives them (row groups: the first
 // launch, whose waves of group 0 zero the mask word of fragments f = 32i and f = 0 the count), instead of
@@ -680,10 +675,6 @@ __device__ __forceinline__ void zero_verdict_words(const RecvSource &src, size_t
     if ((f & 31u) == 0) src.mask[f >> 5] = 0u;
     if (f == 0) *src.nbad = 0u;
 }
-template <class S>
-struct IsGroupRecv : std::false_type {};
-template <>
-struct IsGroupRecv<GroupSource<RecvSource>> : std::true_type {};
 __device__ __forceinline__ void zero_verdict_words(const RecvHdrBase &src, size_t f) {
     if ((f & 31u) == 0) {
         src.hmask[f >> 5] = 0u;
@@ -694,10 +685,14 @@ __device__ __forceinline__ void zero_verdict_words(const RecvHdrBase &src, size_
         src.nbad[1] = 0u;
     }
 }
-template <>
-struct IsGroupRecv<GroupSource<RecvUnpackSource>> : std::true_type {};
-template <>
-struct IsGroupRecv<GroupSource<MsgRecvSource>> : std::true_type {};
+// The row groups whose first launch does so: these three sources' and no other's -- RecvCopyOnlySource's and
+// RecvUnpackCopyOnlySource's verdicts are zeroed by a launch of their own (launch_copy_to_app, launch_recv_hdr).
+template <class S>
+struct IsGroupRecv : std::false_type {};
+template <class S>
+struct IsGroupRecv<GroupSource<S>>
+    : std::integral_constant<bool, std::is_same<S, RecvSource>::value || std::is_same<S, RecvUnpackSource>::value ||
+                                       std::is_same<S, MsgRecvSource>::value> {};
 
 // Byte-balanced descriptor batches (launch_crc_desc / launch_sum_desc for n <= kPlanMax): plan_kernel
 // cuts every fragment longer than the plan's window B into segments of at most B bytes and groups the
@@ -3285,14 +3280,23 @@ __global__ void __launch_bounds__(256) crc_light_group_join_kernel(const Src src
 // and the 4 KiB descriptor lines unchanged (60.6-60.9%, 80.9%: the empty launch costs nothing visible in-stream).
 constexpr unsigned kLeftoverWgs = 256;
 
+// The table-light kernels come in workgroups of 16, 8 and 4 waves (the A/B knobs LAMPI_PAIR_WAVES and
+// LAMPI_LIGHT_WAVES choose): fn(std::integral_constant<int, kWv>) for the one asked for.
+template <class Fn>
+static void with_waves(int waves, Fn &&fn) {
+    if (waves == 16)
+        fn(std::integral_constant<int, 16>{});
+    else if (waves == 8)
+        fn(std::integral_constant<int, 8>{});
+    else
+        fn(std::integral_constant<int, 4>{});
+}
+
 template <class Src>
 static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uint32_t *img, uint32_t *out,
                                              hipStream_t s, uint32_t *shape_nhalf) {
     uint32_t *left = nullptr, *next_left = nullptr, *list = nullptr;
-    static const int kWv = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_PAIR_WAVES");
-        return e && e[0] == '1' ? 16 : e && e[0] == '4' ? 4 : 8;
-    }();
+    static const int kWv = knob_waves(LAMPI_AB_ENV("LAMPI_PAIR_WAVES"), 8);
     const size_t nwg = (n + 2 * kWv - 1) / (2 * kWv);
     bool pooled = false;
     // (one entry per wave at most: a batch whose shape changed since the census leaves every wave)
@@ -3301,15 +3305,11 @@ static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uin
     // the counter pair is taken only now: a failure before this point leaves it untouched
     e = pair_counters(s, &left, &next_left);
     if (e != hipSuccess) return scratch_done(s, list, pooled, e);
-    if (kWv == 16)
-        hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, 16>), dim3((unsigned)nwg), dim3(1024), 0, s, src, n, img, out,
-                           left, list);
-    else if (kWv == 8)
-        hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, 8>), dim3((unsigned)nwg), dim3(512), 0, s, src, n, img, out,
-                           left, list);
-    else
-        hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, 4>), dim3((unsigned)nwg), dim3(256), 0, s, src, n, img, out,
-                           left, list);
+    with_waves(kWv, [&](auto wv) {
+        constexpr int kW = decltype(wv)::value;
+        hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, kW>), dim3((unsigned)nwg), dim3(64 * kW), 0, s, src, n, img,
+                           out, left, list);
+    });
     e = hipGetLastError();
     if (e == hipSuccess) {
         hipLaunchKernelGGL(crc_light_pair_leftover_kernel<Src>, dim3(kLeftoverWgs), dim3(256), 0, s, src, n, img, out,
@@ -3326,12 +3326,8 @@ static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uin
 // box-dependent on the receive step (profiles/r04/light_waves_ab.txt, recv_waves_ab.txt); with the
 // single-row step (95 VGPRs) it lost there too: GM receive 72.2 against 69.0% (profiles/r04/last_row_ab.txt).
 // A/B knob LAMPI_LIGHT_WAVES = 4, 8, 16.
-static int light_waves(bool recv = false) {
-    (void)recv;
-    static const int w = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_LIGHT_WAVES");
-        return e && e[0] == '1' ? 16 : e && e[0] == '8' ? 8 : 4;
-    }();
+static int light_waves() {
+    static const int w = knob_waves(LAMPI_AB_ENV("LAMPI_LIGHT_WAVES"), 4);
     return w;
 }
 
@@ -3347,17 +3343,12 @@ template <class Src>
 static hipError_t launch_crc_light_frag_copy(const Src &src, size_t n, const uint32_t *img, uint32_t *out,
                                              hipStream_t s, uint32_t W = 1) {
     W = light_groups(n, W);
-    const int kWv = light_waves(IsRecv<Src>::value);
     auto launch = [&](size_t items, uint32_t *groups) {
-        if (kWv == 16)
-            hipLaunchKernelGGL((crc_light_frag_copy_kernel<Src, 16>), dim3((unsigned)((items + 15) / 16)), dim3(1024), 0,
-                               s, src, n, img, out, W, groups);
-        else if (kWv == 8)
-            hipLaunchKernelGGL((crc_light_frag_copy_kernel<Src, 8>), dim3((unsigned)((items + 7) / 8)), dim3(512), 0, s,
-                               src, n, img, out, W, groups);
-        else
-            hipLaunchKernelGGL((crc_light_frag_copy_kernel<Src, 4>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s,
-                               src, n, img, out, W, groups);
+        with_waves(light_waves(), [&](auto wv) {
+            constexpr int kW = decltype(wv)::value;
+            hipLaunchKernelGGL((crc_light_frag_copy_kernel<Src, kW>), dim3((unsigned)((items + kW - 1) / kW)),
+                               dim3(64 * kW), 0, s, src, n, img, out, W, groups);
+        });
     };
     if (W <= 1) {
         W = 1;
@@ -5250,7 +5241,7 @@ static hipError_t pair_counters(hipStream_t s, uint32_t **cur, uint32_t **next) 
         slot.left = (uint32_t *)p;
         g_scratch_bytes.fetch_add(kLeftBytes, std::memory_order_relaxed);
     }
-    if (slot.pair_broken) return hipErrorNotReady;  // (learned_rows_hint no longer picks pairs here)
+    if (slot.pair_broken) return hipErrorNotReady;  // (learn_shape no longer picks pairs here)
     const uint32_t par = slot.left_calls++ & 1u;
     *cur = slot.left + par;
     *next = slot.left + (par ^ 1u);
@@ -5372,25 +5363,47 @@ static bool shapes_enabled() {
     return on;
 }
 
-// The rows hint to run this batch with: the caller's, or the one learned from the stream's earlier
+// The entry point a learned shape belongs to: with the descriptor array, the key of its record.  Entry points that
+// share an enumerator share the record of an array.
+enum ShapeKind : int {
+    kShapeFragDesc = 0,         // launch_crc_desc and launch_sum_desc
+    kShapeBcopy = 1,            // launch_bcopy_desc, CRC and SUM
+    kShapeCopyToApp = 2,        // launch_copy_to_app, every mode
+    kShapeBcopyNone = 3,        // launch_bcopy_desc with checksumming off
+    kShapeSendPack = 4,         // launch_send_pack, CRC and SUM
+    kShapeSendPackNone = 5,     // ... with checksumming off
+    kShapeRecvUnpack = 6,       // launch_recv_unpack, CRC and SUM
+    kShapeRecvUnpackNone = 7,   // ... with checksumming off
+};
+
+// What learn_shape found.  Every field but rows keeps its default when nothing was learned: the caller gave a
+// hint, the batch is under kShapeMin fragments, the stream is being captured, or no census has landed yet.
+struct LearnedShape {
+    uint32_t rows = 1;              // the rows hint to run with: the caller's, or the most rows sampled
+    bool pairs = false;             // every sampled fragment at most 2 KiB, and nhalf_dev is set (see ShapeOpts)
+    uint32_t *nhalf_dev = nullptr;  // the record's nhalf as the device sees it (the pair kernel's leftover launch)
+    bool one_row = false;           // every sampled fragment one row (17 B-4 KiB)
+    bool full_rows = false;         // ... the same whole number of rows at a 16-byte-aligned address
+    bool all_half = false;          // ... at most 2 KiB
+    bool all_1k = false;            // ... at most 1 KiB
+    uint32_t contig_len = 0;        // ... where one contiguous run of equal fragments puts it: their length
+};
+struct ShapeOpts {
+    uint32_t min_rows = kShapeRows;      // fewest rows of a learned hint
+    bool pairs_misaligned_only = false;  // pairs only for 1-2 KiB fragments, a quarter ending off the 16-byte grid
+};
+
+// The shape to run this batch with: the caller's rows hint, or what was learned from the stream's earlier
 // batches of this kind (launching the census for later ones when due).
 template <class Src>
-static uint32_t learned_rows_hint(const Src &src, size_t n, hipStream_t s, int kind, uint32_t rows_hint,
-                                  bool *pairs = nullptr, uint32_t **nhalf_dev = nullptr,
-                                  uint32_t min_rows = kShapeRows, bool *one_row = nullptr,
-                                  bool *full_rows = nullptr, bool pairs_misaligned_only = false,
-                                  bool *all_half = nullptr, bool *all_1k = nullptr, uint32_t *contig_len = nullptr) {
-    if (contig_len) *contig_len = 0u;
-    if (all_half) *all_half = false;
-    if (all_1k) *all_1k = false;
-    if (pairs) *pairs = false;
-    if (one_row) *one_row = false;
-    if (full_rows) *full_rows = false;
-    if (rows_hint > 1 || n < kShapeMin || !shapes_enabled()) return rows_hint;
+static LearnedShape learn_shape(const Src &src, size_t n, hipStream_t s, ShapeKind kind, uint32_t rows_hint,
+                                const ShapeOpts &opt = {}) {
+    LearnedShape ls{rows_hint};
+    if (rows_hint > 1 || n < kShapeMin || !shapes_enabled()) return ls;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return rows_hint;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return ls;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return rows_hint;
+    if (hipGetDevice(&dev) != hipSuccess) return ls;
     ScratchTable::Slot &slot = t_scratch.slots[{dev, s}];
     // this batch's record: the one of its descriptor array, else the least recently used one, reset
     static const bool keyed = [] {  // (A/B knob LAMPI_SHAPES_UNKEYED=1: one record per kind, as in round 4)
@@ -5419,7 +5432,7 @@ static uint32_t learned_rows_hint(const Src &src, size_t n, hipStream_t s, int k
         void *p = nullptr;
         if (hipHostMalloc(&p, sizeof(BatchShape), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
             (void)hipGetLastError();
-            return rows_hint;
+            return ls;
         }
         std::memset(p, 0, sizeof(BatchShape));
         rec = (BatchShape *)p;
@@ -5427,32 +5440,26 @@ static uint32_t learned_rows_hint(const Src &src, size_t n, hipStream_t s, int k
     }
     // the last record that landed (seq read before and after the fields: a record being written is skipped)
     const volatile BatchShape *v = rec;
-    uint32_t W = rows_hint;
     const uint32_t q0 = v->seq;
     std::atomic_thread_fence(std::memory_order_acquire);  // the fields are read after the first seq ...
     const uint32_t sampled = v->sampled, rmin = v->rmin, rmax = v->rmax, nhalf = v->nhalf, nwhole = v->nwhole,
                    nmis = v->nmis, n12k = v->n12k, n1k = v->n1k, ncontig = v->ncontig, len0 = v->len0;
     std::atomic_thread_fence(std::memory_order_acquire);  // ... and before the second (a seqlock read)
     if (q0 != 0 && v->seq == q0 && sampled > 0) {
-        if (rmin >= min_rows && rmax <= 2 * rmin) W = rmax;
-        if (one_row && rmin == 1u && rmax == 1u) *one_row = true;  // every sampled fragment one row (17 B-4 KiB)
-        // every sampled fragment the same whole number of rows at a 16-byte-aligned address (*full_rows: the
-        // rows, W the most rows as above)
-        // (the whole-row path lists off-shape fragments through the pair counters: not on a stream whose counters
-        // could not be re-zeroed)
-        if (full_rows && nwhole == sampled && rmin == rmax && !slot.pair_broken) *full_rows = true;
-        if (all_half && nhalf == sampled) *all_half = true;  // every sampled fragment at most 2 KiB
-        if (all_1k && n1k == sampled) *all_1k = true;        // ... at most 1 KiB
-        // every sampled fragment where one contiguous run of equal fragments puts it (packed rows; the pair counters
-        // list the items that are not, so not on a stream whose counters are broken)
-        if (contig_len && ncontig == sampled && !slot.pair_broken) *contig_len = len0;
-        if (pairs && nhalf == sampled && !slot.pair_broken &&
-            (!pairs_misaligned_only || (n12k == sampled && 4 * nmis >= sampled))) {  // every sampled fragment at
-            // most 2 KiB: two per wave (read-only: 1-2 KiB each, a quarter or more ending off the 16-byte grid)
+        if (rmin >= opt.min_rows && rmax <= 2 * rmin) ls.rows = rmax;
+        ls.one_row = rmin == 1u && rmax == 1u;
+        // (the whole-row path, the packed rows and the pairs list off-shape fragments through the pair counters: not
+        // on a stream whose counters could not be re-zeroed)
+        ls.full_rows = nwhole == sampled && rmin == rmax && !slot.pair_broken;  // (rows: how many)
+        ls.all_half = nhalf == sampled;
+        ls.all_1k = n1k == sampled;
+        if (ncontig == sampled && !slot.pair_broken) ls.contig_len = len0;
+        if (nhalf == sampled && !slot.pair_broken &&
+            (!opt.pairs_misaligned_only || (n12k == sampled && 4 * nmis >= sampled))) {  // two fragments per wave
             void *dp = nullptr;
-            if (nhalf_dev && hipHostGetDevicePointer(&dp, rec, 0) == hipSuccess) {
-                *pairs = true;
-                *nhalf_dev = &((BatchShape *)dp)->nhalf;
+            if (hipHostGetDevicePointer(&dp, rec, 0) == hipSuccess) {
+                ls.pairs = true;
+                ls.nhalf_dev = &((BatchShape *)dp)->nhalf;
             } else {
                 (void)hipGetLastError();
             }
@@ -5468,7 +5475,7 @@ static uint32_t learned_rows_hint(const Src &src, size_t n, hipStream_t s, int k
             (void)hipGetLastError();
         }
     }
-    return W;
+    return ls;
 }
 
 template <bool kSum, int kWv, int kCap>
@@ -5548,18 +5555,32 @@ constexpr size_t kSplitMin = 1024, kSplitMax = 65536;
 // chain row by row -- the items holding any other fragment listed by the kernel and checksummed by
 // crc_light_pair_leftover_kernel (the pair kernel's counters and leftover launch).
 constexpr size_t kRegDescMinPairs = 2048;
-constexpr size_t kPackedMinRows = 256;
-constexpr size_t kSumRow4kMinRows = 256;  // sum_row4k_kernel: smaller messages keep the other schedules  // packed rows: smaller batches keep the other schedules (one launch)
+constexpr size_t kPackedMinRows = 256;    // packed rows: smaller batches keep the other schedules (one launch)
+constexpr size_t kSumRow4kMinRows = 256;  // sum_row4k_kernel: smaller messages keep the other schedules
+
+// The sum_row4k_* kernels take equal fragments of 64 B .. 1 KiB, a power of two (L), over nrow whole 4 KiB rows
+// whose row index fits 32 bits; kG = L / 16 lanes own a fragment.
+static bool row4k_len(size_t L) { return L >= 64 && L <= 1024 && (L & (L - 1)) == 0; }
+static bool row4k_rows(size_t nrow) { return nrow >= kSumRow4kMinRows && nrow <= 0xFFFFFFFFull; }
+// fn(std::integral_constant<int, kG>) for a length row4k_len() passed
+template <class Fn>
+static void with_row4k_lanes(size_t L, Fn &&fn) {
+    switch (L) {
+        case 64: fn(std::integral_constant<int, 4>{}); break;
+        case 128: fn(std::integral_constant<int, 8>{}); break;
+        case 256: fn(std::integral_constant<int, 16>{}); break;
+        case 512: fn(std::integral_constant<int, 32>{}); break;
+        default: fn(std::integral_constant<int, 64>{}); break;
+    }
+}
 static uint32_t pick_regular_fpw(size_t n, size_t span);
 static hipError_t launch_crc_desc_whole(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img,
                                         hipStream_t s, uint32_t R) {
     const size_t items = R == 1 ? n / 2 : n;  // pairs of 4 KiB fragments, or fragments
     const size_t span = R == 1 ? 2 * kRowBytes : (size_t)R * kRowBytes;
     if (items > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    static const uint32_t fpw_env = [] {  // (A/B knob LAMPI_DESC_FPW: items per wave)
-        const char *e = LAMPI_AB_ENV("LAMPI_DESC_FPW");
-        return e ? (uint32_t)std::atoi(e) : 0u;
-    }();
+    // (A/B knob LAMPI_DESC_FPW: items per wave)
+    static const uint32_t fpw_env = knob_u32(LAMPI_AB_ENV("LAMPI_DESC_FPW"), 0u);
     uint32_t fpw = pick_regular_fpw(items, span);
     if (fpw_env) {
         fpw = fpw_env;
@@ -5650,21 +5671,17 @@ static hipError_t launch_sum_desc_row4k(const lampi_frag_desc *d, size_t n, uint
                                         hipStream_t s, uint32_t L, size_t *done) {
     *done = 0;
     const size_t F = kRowBytes / L, nrow = n / F;
-    if (nrow < kSumRow4kMinRows || nrow > 0xFFFFFFFFull || nrow * F > 0xFFFFFFFFull) return hipSuccess;
+    if (!row4k_rows(nrow) || nrow * F > 0xFFFFFFFFull) return hipSuccess;
     uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
     bool pooled = false;
     hipError_t e = stream_scratch(s, (nrow * F + 1) * sizeof(uint32_t), (void **)&list, &pooled);
     if (e != hipSuccess) return e;
     e = pair_counters(s, &left, &next_left);
     if (e != hipSuccess) return scratch_done(s, list, pooled, e);
-    const dim3 g((unsigned)nrow);
-    switch (L) {
-        case 64: hipLaunchKernelGGL(sum_row4k_desc_kernel<4>, g, dim3(128), 0, s, d, img, out, list, left); break;
-        case 128: hipLaunchKernelGGL(sum_row4k_desc_kernel<8>, g, dim3(128), 0, s, d, img, out, list, left); break;
-        case 256: hipLaunchKernelGGL(sum_row4k_desc_kernel<16>, g, dim3(128), 0, s, d, img, out, list, left); break;
-        case 512: hipLaunchKernelGGL(sum_row4k_desc_kernel<32>, g, dim3(128), 0, s, d, img, out, list, left); break;
-        default: hipLaunchKernelGGL(sum_row4k_desc_kernel<64>, g, dim3(128), 0, s, d, img, out, list, left); break;
-    }
+    with_row4k_lanes(L, [&](auto kG) {
+        hipLaunchKernelGGL(sum_row4k_desc_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0, s, d, img,
+                           out, list, left);
+    });
     e = hipGetLastError();
     if (e == hipSuccess) {
         hipLaunchKernelGGL(sum_pair_leftover_kernel, dim3(kLeftoverWgs), dim3(256), 0, s, d, nrow * F, out,
@@ -5689,10 +5706,7 @@ static hipError_t launch_sum_desc_row4k(const lampi_frag_desc *d, size_t n, uint
 // (one 64 MiB fragment: 168 us as groups, 55 us with the hint).  A/B knob LAMPI_SMALL_BATCH = the item
 // target (0: the count split).
 static uint32_t small_batch_groups(size_t n, hipStream_t s) {
-    static const size_t target = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SMALL_BATCH");
-        return e ? (size_t)std::atoll(e) : (size_t)4096;
-    }();
+    static const size_t target = knob_size(LAMPI_AB_ENV("LAMPI_SMALL_BATCH"), (size_t)4096);
     // graph captures keep the count split: the groups' scratch would be a pooled allocation inside the graph
     // (bench.py --latency: a replayed one-descriptor call 6.9 -> 32 us)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -5711,39 +5725,32 @@ hipError_t launch_crc_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, co
         const uint32_t W = small_batch_groups(n, s);
         if (W > 1) return launch_crc_light_frag_copy(SparseDescSource{{d}}, n, img, out, s, W);
     }
-    bool whole = false, pairs = false;
-    uint32_t *nhalf = nullptr;
     const uint32_t given = rows_hint;
     // read-only: two fragments per wave only for 1-2 KiB fragments ending off the 16-byte grid (IB's 1,976 B), where
     // the piece streams take their five-load variant (profiles/r05/crc_ro_pairs_ab.txt)
-    bool small = false;
-    uint32_t contig = 0;
-    rows_hint = learned_rows_hint(DescSource{d}, n, s, 0, rows_hint, &pairs, &nhalf, 1u, nullptr, &whole, true, &small,
-                                  nullptr, &contig);
+    ShapeOpts opt;
+    opt.min_rows = 1u;
+    opt.pairs_misaligned_only = true;
+    const LearnedShape sh = learn_shape(DescSource{d}, n, s, kShapeFragDesc, rows_hint, opt);
+    rows_hint = sh.rows;
+    const bool whole = sh.full_rows, small = sh.all_half;
+    const uint32_t contig = sh.contig_len;
     // one contiguous run of equal 64 B .. 2 KiB fragments (a message as descriptors): packed rows, the rest after it
-    static const bool packed_desc = [] {  // (A/B knob LAMPI_PACKED_DESC=0: off)
-        const char *e = LAMPI_AB_ENV("LAMPI_PACKED_DESC");
-        return !(e && e[0] == '0');
-    }();
+    static const bool packed_desc = knob_on(LAMPI_AB_ENV("LAMPI_PACKED_DESC"));  // (A/B knob LAMPI_PACKED_DESC=0: off)
     if (packed_desc && contig >= 64 && contig <= kRowBytes / 2 && (contig & (contig - 1)) == 0) {
         size_t done = 0;
         const hipError_t e = launch_desc_packed<false>(d, n, out, img, s, contig, &done);
         if (e != hipSuccess) return e;
         if (done) return done >= n ? hipSuccess : launch_crc_desc(d + done, n - done, out + done, img, grid, s, false, 1u);
     }
-    static const bool ro_pairs = [] {  // (A/B knob LAMPI_CRC_RO_PAIRS=0: read-only IB-sized batches on the piece streams)
-        const char *e = LAMPI_AB_ENV("LAMPI_CRC_RO_PAIRS");
-        return !(e && e[0] == '0');
-    }();
-    if (pairs && ro_pairs) return launch_crc_light_pair_copy(DescSource{d}, n, img, out, s, nhalf);
+    // (A/B knob LAMPI_CRC_RO_PAIRS=0: read-only IB-sized batches on the piece streams)
+    static const bool ro_pairs = knob_on(LAMPI_AB_ENV("LAMPI_CRC_RO_PAIRS"));
+    if (sh.pairs && ro_pairs) return launch_crc_light_pair_copy(DescSource{d}, n, img, out, s, sh.nhalf_dev);
     // batches of equal whole-row fragments of 1-7 rows on the regular kernel (profiles/r05/crc_desc_pairs_ab.txt:
     // 4 KiB 76.4-77.8 -> 80.3-80.4%, 8 KiB 74.3 -> 77.8%, 16 KiB 74.7 -> 79.2%, 28 KiB 70.4 -> 75.4%; from 8 rows
     // the table-light kernel stays ahead, 32 KiB 81 against 73%, 64 KiB 80 against 67%).  A/B knob
     // LAMPI_CRC_DESC_REGULAR = the most rows taken (0: never).
-    static const uint32_t reg_desc = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_CRC_DESC_REGULAR");
-        return e ? (uint32_t)std::atoi(e) : 7u;
-    }();
+    static const uint32_t reg_desc = knob_u32(LAMPI_AB_ENV("LAMPI_CRC_DESC_REGULAR"), 7u);
     if (whole && rows_hint >= 1u && rows_hint <= reg_desc && n >= 2 * kRegDescMinPairs)
         return launch_crc_desc_whole(d, n, out, img, s, rows_hint);
     if (given <= 1 && rows_hint < kShapeRows) rows_hint = given;  // (learned hints under 8 rows: as before)
@@ -5837,10 +5844,7 @@ hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
     // non-whole-row 65,552-131,056 B on the framed regular kernel (removed) 71-76.5 -> 76-82%.
     // fragments of 64 B .. 2 KiB (powers of two) in packed rows of config B's kernel; the rest of the message
     // (its last fragments) through the schedules below
-    static const bool packed = [] {  // (A/B knob LAMPI_PACKED=0: off)
-        const char *e = LAMPI_AB_ENV("LAMPI_PACKED");
-        return !(e && e[0] == '0');
-    }();
+    static const bool packed = knob_on(LAMPI_AB_ENV("LAMPI_PACKED"));  // (A/B knob LAMPI_PACKED=0: off)
     if (packed) {
         size_t done = 0;
         const hipError_t e = launch_packed<false>(base, msg_len, frag_len, partial, out, img, s, &done);
@@ -5853,10 +5857,8 @@ hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
         }
     }
     const size_t R = (frag_len + kRowBytes - 1) / kRowBytes;
-    static const bool ro_pairs = [] {  // (A/B knob LAMPI_CRC_RO_PAIRS=0, as launch_crc_desc)
-        const char *e = LAMPI_AB_ENV("LAMPI_CRC_RO_PAIRS");
-        return !(e && e[0] == '0');
-    }();
+    // (A/B knob LAMPI_CRC_RO_PAIRS=0, as launch_crc_desc)
+    static const bool ro_pairs = knob_on(LAMPI_AB_ENV("LAMPI_CRC_RO_PAIRS"));
     if (ro_pairs && frag_len > 1024 && frag_len <= kRowBytes / 2 && (frag_len & 15u) != 0 && n >= kShapeMin &&
         pair_counters_ok(s))
         return launch_crc_light_pair_copy(MsgSource{base, msg_len, frag_len, partial}, n, img, out, s, nullptr);
@@ -5915,10 +5917,8 @@ static hipError_t launch_regular(const uint8_t *base, size_t n, size_t frag_len,
 template <bool kSum, int kSub>
 static hipError_t launch_packed_k(const uint8_t *base, size_t nv, uint32_t partial, uint32_t *out, const uint32_t *img,
                                   hipStream_t s) {
-    static const uint32_t fpw_env = [] {  // (A/B knob LAMPI_PACKED_FPW: items per wave)
-        const char *e = LAMPI_AB_ENV("LAMPI_PACKED_FPW");
-        return e ? (uint32_t)std::atoi(e) : 0u;
-    }();
+    // (A/B knob LAMPI_PACKED_FPW: items per wave)
+    static const uint32_t fpw_env = knob_u32(LAMPI_AB_ENV("LAMPI_PACKED_FPW"), 0u);
     // (config B's choice, 12 items per wave; 1 GiB of 1 KiB fragments: 16 items 71.4%, 8 70.6%, 6 70.5-70.9%, 4 66%;
     // a balanced grid of whole rounds of resident workgroups 68.6-71.1%, profiles/r06/packed_fpw.txt; a tapered grid
     // ending on 512-2,048 workgroups of 2-6 items 68-72%, profiles/r06/packed_taper.txt)
@@ -6025,10 +6025,7 @@ static hipError_t launch_sum_copy_groups(const Src &src, size_t n, uint32_t *out
 // (rows off the 16-byte grid) stay on the row items (77.2% against 71.3%).  A/B knobs LAMPI_SUM_CP_GRP_MIN
 // (fewest rows for fragments that are not whole rows, 0 = never groups), LAMPI_SUM_CP_GRP_ROWS (rows per group).
 static uint32_t sum_copy_groups(uint32_t R, bool whole_rows) {
-    static const uint32_t grp_min = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_CP_GRP_MIN");
-        return e ? (uint32_t)std::atoi(e) : 64u;
-    }();
+    static const uint32_t grp_min = knob_u32(LAMPI_AB_ENV("LAMPI_SUM_CP_GRP_MIN"), 64u);
     static const uint32_t grp_rows = [] {
         const char *e = LAMPI_AB_ENV("LAMPI_SUM_CP_GRP_ROWS");
         return e ? (uint32_t)std::max(1, std::atoi(e)) : 1u;
@@ -6037,47 +6034,56 @@ static uint32_t sum_copy_groups(uint32_t R, bool whole_rows) {
     return (R + grp_rows - 1) / grp_rows;
 }
 
+// ---- the fused copies of descriptor batches: one dispatch ------------------------------------------------
+// launch_bcopy_desc, launch_copy_to_app, launch_recv_hdr and launch_send_pack learn the batch's shape and then
+// run the same three schedules: CRC two fragments to a wave (pairs), else CRC one wave per fragment or per row
+// group, else the SUM workgroups / waves (pairs) / row groups.  With checksumming off they call
+// launch_sum_copy_groups themselves, so their copy-only sources are built for the SUM kernels alone.
+static ShapeOpts shape_opts(int mode) { return {mode == LAMPI_CSUM_CRC32 ? kShapeRows : kShapeRowsSum}; }
+
+template <class Src>
+static hipError_t launch_fused_copy(const Src &src, bool crc, size_t n, const uint32_t *img, uint32_t *out,
+                                    hipStream_t s, const LearnedShape &sh) {
+    if (crc && sh.pairs) return launch_crc_light_pair_copy(src, n, img, out, s, sh.nhalf_dev);
+    if (crc) return launch_crc_light_frag_copy(src, n, img, out, s, sh.rows);
+    return launch_sum_copy_groups(src, n, out, s, sh.rows, sh.pairs);  // (pairs: a wave per fragment)
+}
+
+// Whether launch_fused_copy runs the batch as row groups: two launches, the second a join that ends every fragment.
+static bool runs_as_groups(bool crc, size_t n, const LearnedShape &sh) {
+    return crc ? !sh.pairs && light_groups(n, sh.rows) > 1 : sum_groups(n, sh.rows) > 1;
+}
 
 hipError_t launch_bcopy_desc(const lampi_copy_desc *d, size_t n, uint32_t *out, int mode, const uint32_t *img,
                              hipStream_t s, uint32_t rows_hint) {
     if (n == 0) return hipSuccess;
     if (!img) return hipErrorInvalidValue;  // the tables (CRC)
-    bool pairs = false;
-    uint32_t *nhalf = nullptr;
     if (mode == LAMPI_CSUM_NONE) {  // copies only (out: the caller's scratch), the SUM copy schedules
-        rows_hint = learned_rows_hint(CopyOnlySource{d}, n, s, 3, rows_hint, &pairs, &nhalf, kShapeRowsSum);
-        return launch_sum_copy_groups(CopyOnlySource{d}, n, out, s, rows_hint, pairs);
+        const LearnedShape sh = learn_shape(CopyOnlySource{d}, n, s, kShapeBcopyNone, rows_hint, shape_opts(mode));
+        return launch_sum_copy_groups(CopyOnlySource{d}, n, out, s, sh.rows, sh.pairs);
     }
     const bool crc = mode == LAMPI_CSUM_CRC32;
-    uint32_t contig = 0;
     const uint32_t given = rows_hint;
-    rows_hint = learned_rows_hint(CopySource{d}, n, s, 1, rows_hint, &pairs, &nhalf, crc ? kShapeRows : kShapeRowsSum,
-                                  nullptr, nullptr, false, nullptr, nullptr, &contig);
+    const LearnedShape sh = learn_shape(CopySource{d}, n, s, kShapeBcopy, rows_hint, shape_opts(mode));
+    const uint32_t contig = sh.contig_len;
     // SUM copies of equal 64 B .. 1 KiB fragments: one short-lived workgroup per 4 KiB of them (sum_row4k_copy_desc_kernel),
     // the rest after them.  Same box, interleaved (profiles/r06/sum_row4k_cd_ab.txt), of read + write: 1 KiB 69.0 ->
     // 77.3%, 256 B 23.7 -> 77.7%, 64 B 6.9 -> 63.0% (to + 8 / + 1 destinations 58-74%).  A/B knob
     // LAMPI_SUM_ROW4K_COPY_DESC=0: off
-    static const bool row4k_cd = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_ROW4K_COPY_DESC");
-        return !(e && e[0] == '0');
-    }();
-    if (!crc && row4k_cd && given <= 1 && contig >= 64 && contig <= 1024 && (contig & (contig - 1)) == 0) {
+    static const bool row4k_cd = knob_on(LAMPI_AB_ENV("LAMPI_SUM_ROW4K_COPY_DESC"));
+    if (!crc && row4k_cd && given <= 1 && row4k_len(contig)) {
         const size_t F = kRowBytes / contig, nrow = n / F;
-        if (nrow >= kSumRow4kMinRows && nrow * F <= 0xFFFFFFFFull) {
+        if (row4k_rows(nrow) && nrow * F <= 0xFFFFFFFFull) {
             uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
             bool pooled = false;
             hipError_t e = stream_scratch(s, (nrow * F + 1) * sizeof(uint32_t), (void **)&list, &pooled);
             if (e != hipSuccess) return e;
             e = pair_counters(s, &left, &next_left);
             if (e != hipSuccess) return scratch_done(s, list, pooled, e);
-            const dim3 g((unsigned)nrow);
-            switch (contig) {
-                case 64: hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<4>, g, dim3(128), 0, s, d, img, out, list, left); break;
-                case 128: hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<8>, g, dim3(128), 0, s, d, img, out, list, left); break;
-                case 256: hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<16>, g, dim3(128), 0, s, d, img, out, list, left); break;
-                case 512: hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<32>, g, dim3(128), 0, s, d, img, out, list, left); break;
-                default: hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<64>, g, dim3(128), 0, s, d, img, out, list, left); break;
-            }
+            with_row4k_lanes(contig, [&](auto kG) {
+                hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0,
+                                   s, d, img, out, list, left);
+            });
             e = hipGetLastError();
             if (e == hipSuccess) {
                 hipLaunchKernelGGL(sum_copy_list_kernel, dim3(kLeftoverWgs), dim3(128), 0, s, d, (const uint32_t *)left,
@@ -6091,9 +6097,7 @@ hipError_t launch_bcopy_desc(const lampi_copy_desc *d, size_t n, uint32_t *out, 
             return done >= n ? hipSuccess : launch_bcopy_desc(d + done, n - done, out + done, mode, img, s, 1u);
         }
     }
-    if (crc && pairs) return launch_crc_light_pair_copy(CopySource{d}, n, img, out, s, nhalf);
-    if (crc) return launch_crc_light_frag_copy(CopySource{d}, n, img, out, s, rows_hint);
-    return launch_sum_copy_groups(CopySource{d}, n, out, s, rows_hint, pairs);  // (pairs: a wave per fragment)
+    return launch_fused_copy(CopySource{d}, crc, n, img, out, s, sh);
 }
 
 // The receive step's mask words and bad count, zeroed in one launch (two memsets were two ~5 us stream
@@ -6104,6 +6108,13 @@ __global__ void __launch_bounds__(256) zero_verdicts_kernel(uint32_t *__restrict
     if (i < nwords) mask[i] = 0u;
     if (i == 0) *nbad = 0u;
 }
+// ... for n fragments
+static hipError_t zero_verdicts(uint32_t *mask, size_t n, uint32_t *nbad, hipStream_t s) {
+    const size_t nwords = (n + 31) / 32;
+    hipLaunchKernelGGL(zero_verdicts_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, mask, nwords,
+                       nbad);
+    return hipGetLastError();
+}
 
 hipError_t launch_copy_to_app(const lampi_recv_desc *d, size_t n, const uint8_t *expected, size_t exp_stride,
                               int64_t *copied, uint32_t *csum, uint32_t *mask, uint32_t *nbad, int mode,
@@ -6113,34 +6124,21 @@ hipError_t launch_copy_to_app(const lampi_recv_desc *d, size_t n, const uint8_t 
     const bool crc = mode == LAMPI_CSUM_CRC32;
     const RecvSource src{d, crc ? 0xFFFFFFFFu : 0u, expected, exp_stride, copied, mask, nbad};
     if (mode == LAMPI_CSUM_NONE) {  // copy only, every fragment DataOK: the SUM copy schedules without the sums
-        const size_t nwords = (n + 31) / 32;
-        hipLaunchKernelGGL(zero_verdicts_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, mask, nwords,
-                           nbad);
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = zero_verdicts(mask, n, nbad, s);  // (always: its row groups' first launch does not)
         if (e != hipSuccess) return e;
         RecvCopyOnlySource co;
         static_cast<RecvSource &>(co) = src;
-        bool small = false;  // (fragments of at most 2 KiB: a wave each, as SUM)
-        uint32_t *nh = nullptr;
-        rows_hint = learned_rows_hint(co, n, s, 2, rows_hint, &small, &nh, kShapeRowsSum);
-        return launch_sum_copy_groups(co, n, csum, s, rows_hint, small);
+        const LearnedShape sh = learn_shape(co, n, s, kShapeCopyToApp, rows_hint, shape_opts(mode));
+        return launch_sum_copy_groups(co, n, csum, s, sh.rows, sh.pairs);  // (pairs: a wave each, as SUM)
     }
-    bool pairs = false;
-    uint32_t *nhalf = nullptr;
-    rows_hint = learned_rows_hint(src, n, s, 2, rows_hint, &pairs, &nhalf, crc ? kShapeRows : kShapeRowsSum);
+    const LearnedShape sh = learn_shape(src, n, s, kShapeCopyToApp, rows_hint, shape_opts(mode));
     // row groups: the first launch zeroes the verdicts (zero_verdict_words), the join gives them; otherwise
     // the fragments' own waves give them, after this
-    const bool groups = crc ? !pairs && light_groups(n, rows_hint) > 1 : sum_groups(n, rows_hint) > 1;
-    if (!groups) {
-        const size_t nwords = (n + 31) / 32;
-        hipLaunchKernelGGL(zero_verdicts_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, mask, nwords,
-                           nbad);
-        const hipError_t e = hipGetLastError();
+    if (!runs_as_groups(crc, n, sh)) {
+        const hipError_t e = zero_verdicts(mask, n, nbad, s);
         if (e != hipSuccess) return e;
     }
-    if (crc && pairs) return launch_crc_light_pair_copy(src, n, img, csum, s, nhalf);
-    if (crc) return launch_crc_light_frag_copy(src, n, img, csum, s, rows_hint);
-    return launch_sum_copy_groups(src, n, csum, s, rows_hint, pairs);  // (pairs: a wave per fragment)
+    return launch_fused_copy(src, crc, n, img, csum, s, sh);
 }
 
 // ---- the receive step in one call ---------------------------------------------------------------------
@@ -6156,6 +6154,12 @@ __global__ void __launch_bounds__(256) zero_verdicts2_kernel(uint32_t *__restric
         nbad[0] = 0u;
         nbad[1] = 0u;
     }
+}
+static hipError_t zero_verdicts2(uint32_t *hmask, uint32_t *dmask, size_t n, uint32_t *nbad, hipStream_t s) {
+    const size_t nwords = (n + 31) / 32;
+    hipLaunchKernelGGL(zero_verdicts2_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, hmask, dmask,
+                       nwords, nbad);
+    return hipGetLastError();
 }
 
 // The header tests as a pass of their own: one thread per header on a 4 KiB LDS copy of the slice tables (as
@@ -6176,7 +6180,7 @@ __global__ void __launch_bounds__(256) recv_hdr_test_kernel(const uint8_t *__res
 }
 
 // The schedules of launch_copy_to_app over a receive-step source (Src: RecvUnpackSource or MsgRecvSource, Co its twin
-// with checksumming off).  pairs: fragments of at most 2 KiB (CRC two to a wave, SUM / NONE one wave each).
+// with checksumming off).  sh.pairs: fragments of at most 2 KiB (CRC two to a wave, SUM / NONE one wave each).
 // Where the header is tested (profiles/r08/recv_unpack_ab.txt): inside get() -- the wave or
 // workgroup that owns the fragment -- except CRC pairs and the row groups of both modes, where every group's wave or
 // workgroup and every join lane would repeat the test ahead of its first payload load (CRC: sixteen dependent table
@@ -6186,28 +6190,23 @@ __global__ void __launch_bounds__(256) recv_hdr_test_kernel(const uint8_t *__res
 // checksumming off too).
 template <class Co, class Src>
 static hipError_t launch_recv_hdr(Src src, size_t n, uint32_t *csum, const uint32_t *img, hipStream_t s,
-                                  uint32_t rows_hint, bool pairs, uint32_t *nhalf, uint32_t max_len) {
+                                  const LearnedShape &sh, uint32_t max_len) {
     static const int prepass = [] {
         const char *e = LAMPI_AB_ENV("LAMPI_RECV_PREPASS");
         return !e ? 1 : e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
     }();
     const int mode = src.mode;
     const bool crc = mode == LAMPI_CSUM_CRC32, none = mode == LAMPI_CSUM_NONE;
-    const size_t nwords = (n + 31) / 32;
     // row groups: the first launch zeroes the verdicts (zero_verdict_words), the join gives them; otherwise the
-    // fragments' own waves give them, after this
-    const bool groups = none  ? IsGroupRecv<GroupSource<Co>>::value && sum_groups(n, rows_hint) > 1
-                        : crc ? !pairs && light_groups(n, rows_hint) > 1
-                              : sum_groups(n, rows_hint) > 1;
+    // fragments' own waves give them, after this.  (Checksumming off: only a twin whose groups do zero them.)
+    const bool groups = (!none || IsGroupRecv<GroupSource<Co>>::value) && runs_as_groups(crc, n, sh);
     if (!groups) {
-        hipLaunchKernelGGL(zero_verdicts2_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, src.hmask,
-                           src.dmask, nwords, src.nbad);
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = zero_verdicts2(src.hmask, src.dmask, n, src.nbad, s);
         if (e != hipSuccess) return e;
     }
     // (checksumming off: the descriptor form reads no header; the ring form tests the length alone, in get())
     const bool ring = max_len != 0xFFFFFFFFu;
-    const bool pre = prepass == 2 ? !none || ring : prepass == 1 && !none && (groups || (crc && pairs));
+    const bool pre = prepass == 2 ? !none || ring : prepass == 1 && !none && (groups || (crc && sh.pairs));
     RecvHdrRec *rec = nullptr;
     bool pooled = false;
     if (pre) {
@@ -6223,13 +6222,9 @@ static hipError_t launch_recv_hdr(Src src, size_t n, uint32_t *csum, const uint3
     if (none) {  // copy only, every fragment DataOK: the SUM copy schedules without the sums
         Co co;
         static_cast<Src &>(co) = src;
-        e = launch_sum_copy_groups(co, n, csum, s, rows_hint, pairs);
-    } else if (crc && pairs) {
-        e = launch_crc_light_pair_copy(src, n, img, csum, s, nhalf);
-    } else if (crc) {
-        e = launch_crc_light_frag_copy(src, n, img, csum, s, rows_hint);
+        e = launch_sum_copy_groups(co, n, csum, s, sh.rows, sh.pairs);
     } else {
-        e = launch_sum_copy_groups(src, n, csum, s, rows_hint, pairs);  // (pairs: a wave per fragment)
+        e = launch_fused_copy(src, crc, n, img, csum, s, sh);
     }
     return pre ? scratch_done(s, rec, pooled, e) : e;
 }
@@ -6250,7 +6245,7 @@ static void fill_recv_hdr_base(RecvHdrBase &b, const uint8_t *hdrs, size_t hdr_s
 }
 
 // The descriptor form.  The batch's shape is learned as launch_copy_to_app learns it -- the census reads the
-// descriptors through RecvSource, whatever the headers say -- in records of its own (kinds 6 and 7).
+// descriptors through RecvSource, whatever the headers say -- in records of its own (kShapeRecvUnpack*).
 hipError_t launch_recv_unpack(const lampi_recv_desc *d, size_t n, const uint8_t *hdrs, size_t hdr_stride, int kind,
                               int64_t *copied, uint32_t *csum, uint32_t *hmask, uint32_t *dmask, uint32_t *nbad, int mode,
                               const uint32_t *img, hipStream_t s, uint32_t rows_hint) {
@@ -6259,18 +6254,16 @@ hipError_t launch_recv_unpack(const lampi_recv_desc *d, size_t n, const uint8_t 
     RecvUnpackSource src;
     fill_recv_hdr_base(src, hdrs, hdr_stride, kind, mode, img, copied, hmask, dmask, nbad);
     src.d = d;
-    bool pairs = false;
-    uint32_t *nhalf = nullptr;
+    LearnedShape sh;
     if (mode == LAMPI_CSUM_NONE) {
         RecvCopyOnlySource shape;
         static_cast<RecvSource &>(shape) = RecvSource{d, 0u, nullptr, 0, copied, dmask, nbad};
-        rows_hint = learned_rows_hint(shape, n, s, 7, rows_hint, &pairs, &nhalf, kShapeRowsSum);
+        sh = learn_shape(shape, n, s, kShapeRecvUnpackNone, rows_hint, shape_opts(mode));
     } else {
-        const bool crc = mode == LAMPI_CSUM_CRC32;
         const RecvSource shape{d, src.empty, hdrs + kSendDataCsum, hdr_stride, copied, dmask, nbad};
-        rows_hint = learned_rows_hint(shape, n, s, 6, rows_hint, &pairs, &nhalf, crc ? kShapeRows : kShapeRowsSum);
+        sh = learn_shape(shape, n, s, kShapeRecvUnpack, rows_hint, shape_opts(mode));
     }
-    return launch_recv_hdr<RecvUnpackCopyOnlySource>(src, n, csum, img, s, rows_hint, pairs, nhalf, 0xFFFFFFFFu);
+    return launch_recv_hdr<RecvUnpackCopyOnlySource>(src, n, csum, img, s, sh, 0xFFFFFFFFu);
 }
 
 // The ring form: nothing to learn, the slot size says what the fragments can be -- at most 2 KiB: pairs; otherwise
@@ -6296,8 +6289,9 @@ hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slo
             pairs = false;
     }
     const size_t R = (room + kRowBytes - 1) / kRowBytes;
-    const uint32_t rows_hint = R >= (crc ? kShapeRows : kShapeRowsSum) ? (uint32_t)std::min<size_t>(R, 4095) : 1u;
-    return launch_recv_hdr<MsgRecvSource>(src, nslots, csum, img, s, rows_hint, pairs, nullptr, src.max_len);
+    LearnedShape sh{R >= shape_opts(mode).min_rows ? (uint32_t)std::min<size_t>(R, 4095) : 1u};
+    sh.pairs = pairs;  // (nhalf_dev stays null: no census record to correct)
+    return launch_recv_hdr<MsgRecvSource>(src, nslots, csum, img, s, sh, src.max_len);
 }
 
 hipError_t launch_sum64_desc(const lampi_frag_desc *d, size_t n, uint64_t *out, bool phased, hipStream_t s) {
@@ -6333,18 +6327,9 @@ hipError_t launch_sum64_finish(const uint64_t *vals, uint32_t nv, const uint8_t 
 // A/B knobs: LAMPI_SUM_RO_ONEWG = fewest fragments for one per workgroup (0: never), LAMPI_SUM_RO_WGS = the
 // workgroup target, LAMPI_SUM_RO_GROUPS=0 = the round-4 schedules (groups of <= 8 up to 256 rows, segments above).
 static uint32_t sum_ro_groups(size_t n, uint32_t R) {
-    static const size_t onewg = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_RO_ONEWG");
-        return e ? (size_t)std::atoll(e) : (size_t)4096;
-    }();
-    static const size_t wgs = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_RO_WGS");
-        return e ? (size_t)std::atoll(e) : (size_t)65536;
-    }();
-    static const bool r5 = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_RO_GROUPS");
-        return !(e && e[0] == '0');
-    }();
+    static const size_t onewg = knob_size(LAMPI_AB_ENV("LAMPI_SUM_RO_ONEWG"), (size_t)4096);
+    static const size_t wgs = knob_size(LAMPI_AB_ENV("LAMPI_SUM_RO_WGS"), (size_t)65536);
+    static const bool r5 = knob_on(LAMPI_AB_ENV("LAMPI_SUM_RO_GROUPS"));
     if (!r5) return R <= 256u && sum_groups(n, min(R, 8u)) > 1 ? min(R, 8u) : 0xFFFFFFFFu;
     if (onewg && R <= 8u && n >= onewg) return 1u;
     uint32_t W = min(R, 8u);
@@ -6362,42 +6347,36 @@ hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, co
         const uint32_t W = small_batch_groups(n, s);
         if (W > 1) return launch_sum_copy_groups(DescSource{d}, n, out, s, W);
     }
-    bool one_row = false;
-    bool half = false;  // (every sampled fragment at most 2 KiB)
-    uint32_t *nh = nullptr;
-    bool tiny = false;  // (every sampled fragment at most 1 KiB)
-    uint32_t contig = 0;  // (one contiguous run of equal fragments: their length)
-    if (img)
-        rows_hint = learned_rows_hint(DescSource{d}, n, s, 0, rows_hint, &half, &nh, 2u, &one_row, nullptr, false,
-                                      nullptr, &tiny, &contig);
+    LearnedShape sh{rows_hint};
+    if (img) {
+        ShapeOpts opt;
+        opt.min_rows = 2u;
+        sh = learn_shape(DescSource{d}, n, s, kShapeFragDesc, rows_hint, opt);
+        rows_hint = sh.rows;
+    }
+    const bool one_row = sh.one_row, half = sh.pairs, tiny = sh.all_1k;
+    const uint32_t contig = sh.contig_len;
     // one contiguous run of equal 64 B .. 1 KiB fragments: packed rows, as launch_crc_desc (2 KiB: one per wave reads
     // faster, as for messages)
-    static const bool packed_desc = [] {  // (A/B knob LAMPI_PACKED_DESC=0: off, as launch_crc_desc)
-        const char *e = LAMPI_AB_ENV("LAMPI_PACKED_DESC");
-        return !(e && e[0] == '0');
-    }();
+    // (A/B knob LAMPI_PACKED_DESC=0: off, as launch_crc_desc)
+    static const bool packed_desc = knob_on(LAMPI_AB_ENV("LAMPI_PACKED_DESC"));
     // ... on short-lived 4 KiB workgroups (sum_row4k_desc_kernel; profiles/r06/sum_row4k_desc_ab.txt, against the packed
     // rows: 1 KiB 72.0 -> 79.9%, 256 B 63.6 -> 75.5%, 64 B 50.5-56.0 -> 60.4-64.3%).  A/B knob LAMPI_SUM_ROW4K_DESC=0: off
-    static const bool row4k_desc = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_ROW4K_DESC");
-        return !(e && e[0] == '0');
-    }();
-    if (img && row4k_desc && rows_hint <= 1 && contig >= 64 && contig <= 1024 && (contig & (contig - 1)) == 0) {
+    static const bool row4k_desc = knob_on(LAMPI_AB_ENV("LAMPI_SUM_ROW4K_DESC"));
+    if (img && row4k_desc && rows_hint <= 1 && row4k_len(contig)) {
         size_t done = 0;
         const hipError_t e = launch_sum_desc_row4k(d, n, out, img, s, contig, &done);
         if (e != hipSuccess) return e;
         if (done) return done >= n ? hipSuccess : launch_sum_desc(d + done, n - done, out + done, img, grid, s, false, 1u);
     }
-    if (img && packed_desc && rows_hint <= 1 && contig >= 64 && contig <= 1024 && (contig & (contig - 1)) == 0) {
+    if (img && packed_desc && rows_hint <= 1 && row4k_len(contig)) {  // (the same lengths)
         size_t done = 0;
         const hipError_t e = launch_desc_packed<true>(d, n, out, img, s, contig, &done);
         if (e != hipSuccess) return e;
         if (done) return done >= n ? hipSuccess : launch_sum_desc(d + done, n - done, out + done, img, grid, s, false, 1u);
     }
-    static const bool sum_tiny = [] {  // (A/B knob LAMPI_SUM_TINY=0, as launch_sum_msg)
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_TINY");
-        return !(e && e[0] == '0');
-    }();
+    // (A/B knob LAMPI_SUM_TINY=0, as launch_sum_msg)
+    static const bool sum_tiny = knob_on(LAMPI_AB_ENV("LAMPI_SUM_TINY"));
     if (img && sum_tiny && tiny && rows_hint <= 1 && n / 256 >= 256) {  // (as launch_sum_msg: 256 per workgroup)
         hipLaunchKernelGGL((crc_stream_kernel<DescSource, kStreamD, kStreamK, true, kSumWv, kSumCap>),
                            frags_grid(n, 256), dim3(64 * kSumWv), 0, s, DescSource{d}, n, 256u, img, out, nullptr);
@@ -6406,10 +6385,7 @@ hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, co
     // batches the census saw as all <= 2 KiB fragments: one fragment per wave, four to a workgroup
     // (sum_copy_waves_kernel, IB's SUM copies' schedule; profiles/r05/sum_ro_waves_ab.txt: 1,976 B 45.5 -> 69.5%,
     // 1 KiB 35.6 -> 64.3%, 2 KiB 58.5 -> 80.4%, 256 B 10.2 -> 20.8%).  A/B knob LAMPI_SUM_RO_WAVES=0: off.
-    static const bool ro_waves = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_RO_WAVES");
-        return !(e && e[0] == '0');
-    }();
+    static const bool ro_waves = knob_on(LAMPI_AB_ENV("LAMPI_SUM_RO_WAVES"));
     if (img && ro_waves && half && rows_hint <= 1) {
         launch_sum_copy(DescSource{d}, n, out, s, true);
         return hipGetLastError();
@@ -6428,10 +6404,7 @@ hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, co
     // workgroups of two fragments each (profiles/r04/sum_ro_wg_ab.txt: 4 KiB descriptors 79.6 -> 86.3%; one per
     // workgroup 83.2%, four 82.7%; config C's mixed sizes lost 0.5 on it and keep the piece streams).  A/B knob
     // LAMPI_SUM_RO_WG = fragments per workgroup (0: off).
-    static const uint32_t ro_wg = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_RO_WG");
-        return e ? (uint32_t)std::atoi(e) : 2u;
-    }();
+    static const uint32_t ro_wg = knob_u32(LAMPI_AB_ENV("LAMPI_SUM_RO_WG"), 2u);
     if (img && ro_wg && one_row && rows_hint <= 1) {
         hipLaunchKernelGGL(sum_copy_wg_kernel<DescSource>,
                            dim3((unsigned)std::min<size_t>((n + ro_wg - 1) / ro_wg, kMaxWgGrid)), dim3(kSumWgThreads), 0,
@@ -6460,40 +6433,23 @@ hipError_t launch_sum_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
     // config D's shard 0 (64 GiB of 16 KiB) 79.8-79.9 -> 86.6-87.2%; 32 KiB 77 -> 86%; GM's 65,456 B 76.6 ->
     // 84.6%; 1 MiB 77.2 -> 88.4%.  A/B knobs LAMPI_SUM_MSG_WG = fragments per workgroup (0: off),
     // LAMPI_SUM_MSG_MAX = the longest fragment taken (bytes).
-    static const uint32_t msg_wg = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_MSG_WG");
-        return e ? (uint32_t)std::atoi(e) : 1u;
-    }();
-    static const size_t msg_max = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_MSG_MAX");
-        return e ? (size_t)std::atoll(e) : ~(size_t)0;
-    }();
+    static const uint32_t msg_wg = knob_u32(LAMPI_AB_ENV("LAMPI_SUM_MSG_WG"), 1u);
+    static const size_t msg_max = knob_size(LAMPI_AB_ENV("LAMPI_SUM_MSG_MAX"), ~(size_t)0);
     // fragments of 64 B .. 1 KiB (powers of two) in packed rows of config B's kernel (2 KiB: one per wave reads
     // faster, below); the message's last fragments through the schedules below
-    static const size_t packed_max = [] {  // (A/B knob LAMPI_PACKED_SUM = the longest fragment taken, 0: off)
-        const char *e = LAMPI_AB_ENV("LAMPI_PACKED_SUM");
-        return e ? (size_t)std::atoll(e) : (size_t)1024;
-    }();
+    // (A/B knob LAMPI_PACKED_SUM = the longest fragment taken, 0: off)
+    static const size_t packed_max = knob_size(LAMPI_AB_ENV("LAMPI_PACKED_SUM"), (size_t)1024);
     // fragments of 64 B .. 1 KiB (powers of two): one short-lived workgroup per 4 KiB of the message (sum_row4k_kernel),
     // the message's last fragments (past its last whole 4 KiB) through the schedules below.  Same box, interleaved
     // (profiles/r06/sum_row4k_ab.txt), against the packed rows: 1 GiB of 1 KiB (config A's shape) 74.0 -> 83.1%, 512 B
     // 70.9 -> 81.8%, 256 B 67.7 -> 82.0%, 64 B 61.9 -> 76.8%; 16 GiB of 1 KiB 77.3 -> 84.7%.  A/B knob
     // LAMPI_SUM_ROW4K=0: off (the packed rows below)
-    static const bool row4k = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_ROW4K");
-        return !(e && e[0] == '0');
-    }();
-    if (row4k && frag_len >= 64 && frag_len <= 1024 && (frag_len & (frag_len - 1)) == 0 &&
-        msg_len / kRowBytes >= kSumRow4kMinRows && msg_len / kRowBytes <= 0xFFFFFFFFull) {
+    static const bool row4k = knob_on(LAMPI_AB_ENV("LAMPI_SUM_ROW4K"));
+    if (row4k && row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
         const size_t nrow = msg_len / kRowBytes, done = nrow * (kRowBytes / frag_len);
-        const dim3 g((unsigned)nrow);
-        switch (frag_len) {
-            case 64: hipLaunchKernelGGL(sum_row4k_kernel<4>, g, dim3(128), 0, s, base, out); break;
-            case 128: hipLaunchKernelGGL(sum_row4k_kernel<8>, g, dim3(128), 0, s, base, out); break;
-            case 256: hipLaunchKernelGGL(sum_row4k_kernel<16>, g, dim3(128), 0, s, base, out); break;
-            case 512: hipLaunchKernelGGL(sum_row4k_kernel<32>, g, dim3(128), 0, s, base, out); break;
-            default: hipLaunchKernelGGL(sum_row4k_kernel<64>, g, dim3(128), 0, s, base, out); break;
-        }
+        with_row4k_lanes(frag_len, [&](auto kG) {
+            hipLaunchKernelGGL(sum_row4k_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0, s, base, out);
+        });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess || done >= n) return e;
         return launch_sum_msg(base + done * frag_len, msg_len - done * frag_len, frag_len, n - done, out + done, img,
@@ -6523,17 +6479,11 @@ hipError_t launch_sum_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
         if (W < 0xFFFFFFFFu) return launch_sum_copy_groups(src, n, out, s, W);
     }
     // fragments of at most 2 KiB one per wave (as launch_sum_desc: 1,976 B 51.2 -> 74.9%, 2 KiB 68 -> 84.2%)
-    static const bool ro_waves = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_RO_WAVES");
-        return !(e && e[0] == '0');
-    }();
+    static const bool ro_waves = knob_on(LAMPI_AB_ENV("LAMPI_SUM_RO_WAVES"));
     // messages of fragments up to 1 KiB: the SUM piece streams with 256 fragments per workgroup (many fragments
     // share a row; profiles/r05/sum_tiny_ab.txt: 64 B 6.5 -> 19.8%, 256 B 22.8 -> 48.6%, 512 B 44.7 -> 67.6%,
     // 1 KiB 70.2 -> 72.4%).  A/B knob LAMPI_SUM_TINY = the longest fragment taken (0: off).
-    static const uint32_t tiny_max = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_TINY");
-        return e ? (uint32_t)std::atoi(e) : 1024u;
-    }();
+    static const uint32_t tiny_max = knob_u32(LAMPI_AB_ENV("LAMPI_SUM_TINY"), 1024u);
     if (img && frag_len <= tiny_max && n / 256 >= 256) {
         hipLaunchKernelGGL((crc_stream_kernel<MsgSource, kStreamD, kStreamK, true, kSumWv, kSumCap>),
                            frags_grid(n, 256), dim3(64 * kSumWv), 0, s, MsgSource{base, msg_len, frag_len, 0u}, n, 256u,
@@ -6582,17 +6532,12 @@ static hipError_t launch_crc_light_copy(const uint8_t *base, size_t msg_len, siz
                                         hipStream_t s) {
     const uint32_t R = (uint32_t)((frag_len + kRowBytes - 1) / kRowBytes);
     const size_t items = n * R;
-    const int kWv = light_waves();
     auto launch = [&](uint32_t *o) {
-        if (kWv == 16)
-            hipLaunchKernelGGL(crc_light_copy_kernel<16>, dim3((unsigned)((items + 15) / 16)), dim3(1024), 0, s, base,
-                               msg_len, (uint32_t)frag_len, R, items, partial, dst, dst_stride, img, o);
-        else if (kWv == 8)
-            hipLaunchKernelGGL(crc_light_copy_kernel<8>, dim3((unsigned)((items + 7) / 8)), dim3(512), 0, s, base,
-                               msg_len, (uint32_t)frag_len, R, items, partial, dst, dst_stride, img, o);
-        else
-            hipLaunchKernelGGL(crc_light_copy_kernel<4>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, base,
-                               msg_len, (uint32_t)frag_len, R, items, partial, dst, dst_stride, img, o);
+        with_waves(light_waves(), [&](auto wv) {
+            constexpr int kW = decltype(wv)::value;
+            hipLaunchKernelGGL(crc_light_copy_kernel<kW>, dim3((unsigned)((items + kW - 1) / kW)), dim3(64 * kW), 0, s,
+                               base, msg_len, (uint32_t)frag_len, R, items, partial, dst, dst_stride, img, o);
+        });
     };
     if (R == 1) {
         launch(out);
@@ -6632,6 +6577,16 @@ static hipError_t zero_words(uint32_t *out, size_t n, hipStream_t s) {
     return hipGetLastError();
 }
 
+// sum_row4k_copy_kernel over the message's nrow whole 4 KiB rows (row4k_len(frag_len), row4k_rows(nrow))
+static hipError_t launch_sum_row4k_copy(const uint8_t *base, size_t nrow, size_t frag_len, uint8_t *dst,
+                                        size_t dst_stride, uint32_t *out, hipStream_t s) {
+    with_row4k_lanes(frag_len, [&](auto kG) {
+        hipLaunchKernelGGL(sum_row4k_copy_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0, s, base, dst,
+                           dst_stride, out);
+    });
+    return hipGetLastError();
+}
+
 hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint8_t *dst,
                             size_t dst_stride, size_t n, uint32_t *out, int mode, const uint32_t *img, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -6644,22 +6599,10 @@ hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len
         // packed rows (launch_crc_msg); the fragments past the last whole 4 KiB through the schedules below.  Same box,
         // interleaved (profiles/r06/crc_copy_2pass_ab.txt), against the one-pass table-light copy, of read + write:
         // 1 KiB 33.9 -> 52.1%, 256 B 9.0 -> 49.5%, 64 B 2.3 -> 48.4%.  A/B knob LAMPI_CRC_COPY_2PASS=0: off
-        static const bool two_pass = [] {
-            const char *e = LAMPI_AB_ENV("LAMPI_CRC_COPY_2PASS");
-            return !(e && e[0] == '0');
-        }();
-        if (two_pass && frag_len >= 64 && frag_len <= 1024 && (frag_len & (frag_len - 1)) == 0 &&
-            msg_len / kRowBytes >= kSumRow4kMinRows && msg_len / kRowBytes <= 0xFFFFFFFFull) {
+        static const bool two_pass = knob_on(LAMPI_AB_ENV("LAMPI_CRC_COPY_2PASS"));
+        if (two_pass && row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
             const size_t nrow = msg_len / kRowBytes, done = nrow * (kRowBytes / frag_len);
-            const dim3 g((unsigned)nrow);
-            switch (frag_len) {
-                case 64: hipLaunchKernelGGL(sum_row4k_copy_kernel<4>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-                case 128: hipLaunchKernelGGL(sum_row4k_copy_kernel<8>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-                case 256: hipLaunchKernelGGL(sum_row4k_copy_kernel<16>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-                case 512: hipLaunchKernelGGL(sum_row4k_copy_kernel<32>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-                default: hipLaunchKernelGGL(sum_row4k_copy_kernel<64>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-            }
-            hipError_t e = hipGetLastError();
+            hipError_t e = launch_sum_row4k_copy(base, nrow, frag_len, dst, dst_stride, out, s);
             if (e == hipSuccess) e = launch_crc_msg(base, nrow * kRowBytes, frag_len, partial, done, out, img, 0, s);
             if (e != hipSuccess || done >= n) return e;
             return launch_msg_bcopy(base + done * frag_len, msg_len - done * frag_len, frag_len, partial,
@@ -6676,22 +6619,10 @@ hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len
     // (sum_row4k_copy_kernel), the fragments past the last whole 4 KiB through the schedules below.  Same box,
     // interleaved (profiles/r06/sum_row4k_copy_ab.txt), against one workgroup per fragment, of read + write: 1 KiB
     // 56.4 -> 79.3%, 256 B 17.2 -> 78.2%, 64 B 5.0 -> 79.2%.  A/B knob LAMPI_SUM_ROW4K_COPY=0: off
-    static const bool row4k_copy = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_ROW4K_COPY");
-        return !(e && e[0] == '0');
-    }();
-    if (row4k_copy && mode == LAMPI_CSUM_SUM32 && frag_len >= 64 && frag_len <= 1024 && (frag_len & (frag_len - 1)) == 0 &&
-        msg_len / kRowBytes >= kSumRow4kMinRows && msg_len / kRowBytes <= 0xFFFFFFFFull) {
+    static const bool row4k_copy = knob_on(LAMPI_AB_ENV("LAMPI_SUM_ROW4K_COPY"));
+    if (row4k_copy && mode == LAMPI_CSUM_SUM32 && row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
         const size_t nrow = msg_len / kRowBytes, done = nrow * (kRowBytes / frag_len);
-        const dim3 g((unsigned)nrow);
-        switch (frag_len) {
-            case 64: hipLaunchKernelGGL(sum_row4k_copy_kernel<4>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-            case 128: hipLaunchKernelGGL(sum_row4k_copy_kernel<8>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-            case 256: hipLaunchKernelGGL(sum_row4k_copy_kernel<16>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-            case 512: hipLaunchKernelGGL(sum_row4k_copy_kernel<32>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-            default: hipLaunchKernelGGL(sum_row4k_copy_kernel<64>, g, dim3(128), 0, s, base, dst, dst_stride, out); break;
-        }
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = launch_sum_row4k_copy(base, nrow, frag_len, dst, dst_stride, out, s);
         if (e != hipSuccess || done >= n) return e;
         return launch_msg_bcopy(base + done * frag_len, msg_len - done * frag_len, frag_len, partial,
                                 dst + done * dst_stride, dst_stride, n - done, out + done, mode, img, s);
@@ -6771,7 +6702,7 @@ hipError_t launch_scatter_u32(const uint32_t *vals, size_t n, uint8_t *dst, size
 // The send step over descriptors (lampi_send_pack_batch): launch_bcopy_desc's dispatch of CopySource on SendSource,
 // whose emit stamps the header -- the table-light kernel one wave per fragment and the SUM workgroups / waves / row
 // groups (the join kernel's emit stamps); checksumming off: the plain copy schedules, IB's zeros from their emit.
-// Learned shapes are kept apart from the copy batches' (kinds 4 and 5).
+// Learned shapes are kept apart from the copy batches' (kShapeSendPack*).
 // Two CRC classes take two launches instead -- CopySource's kernels with the checksums in pooled scratch, then
 // send_stamp_kernel -- because the fused route measured slower there (profiles/r07/send_pack_ab_fused.txt, line B,
 // against profiles/r07/send_pack_ab.txt, line B; A = round 6's sequence of four entry points):
@@ -6806,26 +6737,19 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
     };
     if (fused == 0)
         return two_launches([&](uint32_t *vals) { return launch_bcopy_desc(d, n, vals, mode, img, s, rows_hint); });
-    bool pairs = false;
-    uint32_t *nhalf = nullptr;
     if (mode == LAMPI_CSUM_NONE) {
         SendCopyOnlySource co;
         static_cast<SendSource &>(co) = SendSource{d, hdrs, hdr_stride, img, kind, mode};
-        rows_hint = learned_rows_hint(co, n, s, 5, rows_hint, &pairs, &nhalf, kShapeRowsSum);
-        return launch_sum_copy_groups(co, n, nullptr, s, rows_hint, pairs);
+        const LearnedShape sh = learn_shape(co, n, s, kShapeSendPackNone, rows_hint, shape_opts(mode));
+        return launch_sum_copy_groups(co, n, nullptr, s, sh.rows, sh.pairs);
     }
     const bool crc = mode == LAMPI_CSUM_CRC32;
     const SendSource src{d, hdrs, hdr_stride, img, kind, mode};
-    rows_hint = learned_rows_hint(src, n, s, 4, rows_hint, &pairs, &nhalf, crc ? kShapeRows : kShapeRowsSum);
-    if (crc && pairs && fused != 2)
-        return two_launches(
-            [&](uint32_t *vals) { return launch_crc_light_pair_copy(CopySource{d}, n, img, vals, s, nhalf); });
-    if (crc && fused != 2 && light_groups(n, rows_hint) > 1)
-        return two_launches(
-            [&](uint32_t *vals) { return launch_crc_light_frag_copy(CopySource{d}, n, img, vals, s, rows_hint); });
-    if (crc && pairs) return launch_crc_light_pair_copy(src, n, img, nullptr, s, nhalf);
-    if (crc) return launch_crc_light_frag_copy(src, n, img, nullptr, s, rows_hint);
-    return launch_sum_copy_groups(src, n, nullptr, s, rows_hint, pairs);  // (pairs: a wave per fragment)
+    const LearnedShape sh = learn_shape(src, n, s, kShapeSendPack, rows_hint, shape_opts(mode));
+    // the two CRC classes of two launches (above): the same schedule on CopySource, its values to scratch
+    if (crc && fused != 2 && (sh.pairs || runs_as_groups(crc, n, sh)))
+        return two_launches([&](uint32_t *vals) { return launch_fused_copy(CopySource{d}, crc, n, img, vals, s, sh); });
+    return launch_fused_copy(src, crc, n, img, nullptr, s, sh);
 }
 
 // The send step over a message (lampi_msg_send_pack): launch_msg_bcopy unchanged -- every tuned message schedule,
@@ -6872,9 +6796,8 @@ hipError_t launch_chain(const lampi_copy_desc *d, size_t npieces, const uint32_t
         mode = LAMPI_CSUM_SUM32;
     }
     if (v.copied) {
-        const size_t nwords = (nfrags + 31) / 32;
-        hipLaunchKernelGGL(zero_verdicts_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, v.mask, nwords,
-                           v.nbad);
+        const hipError_t e = zero_verdicts(v.mask, nfrags, v.nbad, s);
+        if (e != hipSuccess) return e;
     }
     constexpr uint32_t kSmall = 256;  // pieces up to this many bytes: one thread each
     const bool sum = mode != LAMPI_CSUM_CRC32;

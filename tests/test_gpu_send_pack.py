@@ -242,7 +242,7 @@ def _learned_sequence(cuda, r, prepared, order, kind, mode):
 def test_learned_schedules(cuda, oracle, kind, mode):
     """IB-sized batches until the census picks the pair kernel (CRC: the pair copy into pooled values, then
     send_stamp_kernel<false>) / a wave per fragment (SUM: SendSource, off: SendCopyOnlySource on
-    sum_copy_waves_kernel, learned-shape kind 5), then batches of 2,049-70,000 bytes in the same descriptor array
+    sum_copy_waves_kernel, kShapeSendPackNone), then batches of 2,049-70,000 bytes in the same descriptor array
     on the same stream -- all four under the stale shape, every wave's fragments left to the leftover launch --
     then IB again; every call checked byte for byte."""
     rng = np.random.default_rng(720 + mode)

@@ -240,6 +240,91 @@ def test_learned_pairs_receive(cuda, oracle, odd, mode):
             assert torch.equal(app[good], want_app[good]), i
 
 
+def _checksum_off_lengths(rng, n, shape):
+    """IB-sized fragments with a few the wave-per-fragment schedule takes as they come (`ib`: the learned shape is
+    "every sampled fragment at most 2 KiB"), or GM-sized ones of 8-16 rows (`gm`: the learned shape is a rows hint,
+    so every fragment runs as row groups -- one past a group boundary by a byte among them)."""
+    if shape == "ib":
+        return _ib_lengths(rng, n, True)
+    ln = np.where(rng.random(n) < 0.7, 65456, rng.integers(28673, 65537, size=n)).astype(np.uint64)
+    ln[n // 2 + 1] = 32768 + 1
+    return ln
+
+
+@pytest.mark.parametrize("shape", ["ib", "gm"])
+def test_learned_copies_checksum_off(cuda, shape):
+    """LAMPI_CSUM_NONE copies (lampi_frag_bcopy_batch) once the census has seen the batch: the learned shape picks
+    a wave per fragment (IB-sized) or row groups (GM-sized) on the copy-only source; no checksum comes back, and
+    every call's destination is compared byte for byte -- the copied bytes and the untouched ones around them."""
+    import torch
+
+    dv = _dv()
+    rng = np.random.default_rng(131 + (shape == "gm"))
+    n = 301
+    ln = _checksum_off_lengths(rng, n, shape)
+    cl = np.where(rng.random(n) < 0.2, ln - np.minimum(ln, rng.integers(0, 24, size=n).astype(np.uint64)), ln)
+    src = torch.empty(n * 70016 + 64, dtype=torch.uint8, device=cuda)
+    dv.fill_stream(src, seed=132)
+    host = src.cpu().numpy()
+    offs = np.arange(n, dtype=np.uint64) * 70016 + rng.integers(0, 16, size=n).astype(np.uint64)
+    dst = torch.empty(n * 70016 + 64, dtype=torch.uint8, device=cuda)
+    doffs = np.arange(n, dtype=np.uint64) * 70016 + rng.integers(0, 16, size=n).astype(np.uint64)
+    descs = dv.make_copy_descs(src, offs, dst, doffs, cl, ln)
+    want_dst = np.full(dst.numel(), 0x5C, np.uint8)
+    for i in range(n):
+        a, b, c = int(offs[i]), int(doffs[i]), int(cl[i])
+        want_dst[b:b + c] = host[a:a + c]
+    want_dst = torch.from_numpy(want_dst).to(cuda)
+    stream = torch.cuda.Stream(device=cuda)
+    with torch.cuda.stream(stream):
+        for i in range(20):
+            dst.fill_(0x5C)
+            assert dv.frag_bcopy_batch(descs, mode=dv.NONE, stream=stream) is None
+            assert torch.equal(dst, want_dst), i
+
+
+@pytest.mark.parametrize("shape", ["ib", "gm"])
+def test_learned_receive_checksum_off(cuda, shape):
+    """CopyToApp with LAMPI_CSUM_NONE once the census has seen the batch (a wave per fragment / row groups on the
+    copy-only source): every fragment DataOK whatever its header says -- lengthToCopy, checksum 0, an empty mask and
+    count, zeroed on every call -- and every application byte, the untouched ones included."""
+    import torch
+
+    from oracle.oracle import copy_to_app_nochecksum
+
+    dv = _dv()
+    rng = np.random.default_rng(141 + (shape == "gm"))
+    n = 301
+    ln = _checksum_off_lengths(rng, n, shape)
+    frag = torch.empty(n * 70016 + 64, dtype=torch.uint8, device=cuda)
+    dv.fill_stream(frag, seed=142)
+    host = frag.cpu().numpy()
+    offs = np.arange(n, dtype=np.uint64) * 70016 + 8
+    app = torch.empty(n * 70016, dtype=torch.uint8, device=cuda)
+    aoffs = np.arange(n, dtype=np.uint64) * 70016 + rng.integers(0, 8, size=n).astype(np.uint64)
+    app_len = np.where(rng.random(n) < 0.1, ln.astype(np.int64) - 30, ln.astype(np.int64) + 3)
+    descs = dv.make_recv_descs(frag, offs, app, aoffs, ln, app_len)
+    want_app = np.full(app.numel(), 0x5C, np.uint8)
+    want_copied = np.zeros(n, np.int64)
+    for i in range(n):
+        a, b, L = int(offs[i]), int(aoffs[i]), int(ln[i])
+        copied, csum, data = copy_to_app_nochecksum(host[a:a + L], L, int(app_len[i]))
+        assert csum == 0
+        want_copied[i] = copied
+        want_app[b:b + data.size] = data
+    want_app = torch.from_numpy(want_app).to(cuda)
+    stream = torch.cuda.Stream(device=cuda)
+    with torch.cuda.stream(stream):
+        for i in range(20):
+            app.fill_(0x5C)
+            copied, got, mask, nbad = dv.copy_to_app_batch(descs, None, mode=dv.NONE, stream=stream)
+            assert not dv.as_u32(got).any(), i
+            assert not dv.mask_bits(mask, n).any(), i
+            assert int(nbad.item()) == 0, i
+            assert np.array_equal(copied.cpu().numpy(), want_copied), i
+            assert torch.equal(app, want_app), i
+
+
 @pytest.mark.parametrize("mode", [0, 1], ids=["crc", "sum"])
 def test_learned_pairs_shape_change(cuda, oracle, mode):
     """IB-sized copies until the census picks pairs, then batches of larger fragments on the same stream
