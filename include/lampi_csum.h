@@ -399,7 +399,7 @@ int lampi_msg_bcopy_strided(const void *d_msg, size_t msg_len, size_t frag_len, 
  * hold it are checksummed into `checksum`.  The 72-byte data header is the same for
  * gmHeaderData and ibDataHdr_t (gm/header.h:56-70, ib/header.h:48-62): dataLength u32 @20,
  * frag_seq u64 @32, sendFragDescPtr u64 @48, dataSeqOffset u64 @56, dataChecksum u32 @64,
- * checksum u32 @68.  (Quadrics' 128-byte header is not covered.)
+ * checksum u32 @68.  Quadrics' 128-byte quadricsCtlHdr_t is the third kind, described after the two.
  *
  * hdr_kind says what the two words get; v = bcopy_uicrc / bcopy_uicsum of the fragment, H = the
  * header's first 68 bytes with the word @64 already stored:
@@ -411,10 +411,43 @@ int lampi_msg_bcopy_strided(const void *d_msg, size_t msg_len, size_t frag_len, 
  *     CRC32 / SUM32: @64 = v, or 0 for a fragment of length 0 (max(copylen, csumlen) == 0);
  *                    @68 = uicrc(H, 68) as it is (not swapped), or uicsum(H, 68) of a fresh state.
  *     NONE:          the payload is copied, @64 = 0 and @68 = 0.
+ *
+ *   LAMPI_SEND_HDR_QUADRICS (quadrics/header.h:71-87, :164-179; sendFrag.h:766-880, :970-986)
+ *     The MESSAGE_DATA header is 128 bytes.  Up to offset 64 its fields sit where GM's and IB's do; then
+ *     dataChecksum u32 @64, dataElanAddr u32 @68, data[52] @72..123 (CTLHDR_DATABYTES = 52), checksum u32 @124.
+ *     A fragment of at most 52 bytes travels inside the header, so the header checksum covers payload bytes
+ *     the same call has just written; a longer fragment from Elan-addressable memory is not copied at all.
+ *     With len = max(copylen, csumlen) and v = bcopy_uicrc / bcopy_uicsum (or uicrc / uicsum) of the fragment
+ *     (partial honoured in CRC mode):
+ *
+ *       fragment                         CRC32 / SUM32                          NONE
+ *       len == 0                         no copy, @64 left as the caller        the same
+ *                                        filled it
+ *       0 < len <= 52 (inline)           copylen bytes to header + 72 (dst is   copylen bytes to header + 72;
+ *                                        ignored), @64 = v, the rest of data[]  @64 = 0 when copylen > 0, else
+ *                                        left as it is                          untouched
+ *       len > 52, copylen > 0            copy to dst, @64 = v                   copy to dst, @64 = 0
+ *         (packBuffer)
+ *       len > 52, copylen == 0           nothing copied, @64 = uicrc / uicsum   nothing read, @64 untouched
+ *         (Elan-addressable)             of the source
+ *       then @124                        headerChecksum(H, 124, 32) over the    0 (sendFrag.h:768)
+ *                                        header as it now stands, that word
+ *                                        taken as 0: bswap32(uicrc(H, 124)),
+ *                                        or the sum of words 0..30
+ *
+ *     One deliberate departure: with quadricsDoChecksum off the reference's contiguous inline branch
+ *     (sendFrag.h:842-851) still computes a checksum in usecrc()'s mode, which no receiver reads
+ *     (recvFrag.h:111).  This library cannot know that mode and stores packBuffer's 0.
+ *     The receiver (path.cc:839-900, recvFrag.h:54-126, recvFrag.cc:150-160) requires uicrc(H, 128) == 0 in
+ *     CRC mode, or the sum of the 32 words == 2 x the word @124 in SUM mode, and reads a payload of 1..52
+ *     bytes from header + 72.
+ *
+ * The value 2 is not a kind: every entry point rejects it.
  * ---------------------------------------------------------------------------------- */
 enum lampi_send_hdr_kind {
     LAMPI_SEND_HDR_GM = 0,
-    LAMPI_SEND_HDR_IB = 1
+    LAMPI_SEND_HDR_IB = 1,
+    LAMPI_SEND_HDR_QUADRICS = 3
 };
 
 /* Descriptor form.  Header i is at (char *)d_hdrs + i*hdr_stride (d_hdrs and hdr_stride 4-byte aligned,
@@ -425,7 +458,12 @@ enum lampi_send_hdr_kind {
  * No allocation and no scatter launch: the wave (or join thread) that finishes a fragment stamps its header,
  * as lampi_copy_to_app_batch gives its verdict -- except CRC batches of IB-sized fragments or of row groups,
  * which measured faster as the copy kernels plus one stamp launch over pooled scratch.
- * n == 0 returns 0.  d_hdrs may be NULL only for GM with LAMPI_CSUM_NONE (nothing is written there). */
+ * n == 0 returns 0.  d_hdrs may be NULL only for GM with LAMPI_CSUM_NONE (nothing is written there).
+ * LAMPI_SEND_HDR_QUADRICS: hdr_stride >= 128 and d_hdrs is required in every mode (NONE writes there too); bytes
+ * [0, 64) and [68, 124) of each header are already filled (dataElanAddr is the caller's) and exactly the bytes of
+ * the table above are written.  A dst range that overlaps any header is the caller's error.  Always two launches:
+ * the copy / checksum kernels with an inline fragment's dst turned to header + 72, then one stamp launch over the
+ * headers as they then stand. */
 int lampi_send_pack_batch(const lampi_copy_desc *d_descs, size_t n, void *d_hdrs, size_t hdr_stride,
                           int hdr_kind, int mode, void *stream);
 
@@ -443,7 +481,14 @@ typedef struct lampi_send_hdr_fill {
 /* Fragments d_msg as lampi_msg_csum does (msg_len == 0: one empty fragment, its header still written),
  * copies fragment k to d_ring + k*slot_stride + 72 with its checksum fused (every fragment from
  * CRC_INITIAL_REGISTER / a fresh state) and writes all 72 header bytes at d_ring + k*slot_stride.
- * d_ring and slot_stride 8-byte aligned, slot_stride >= 72 + frag_len, 1 <= frag_len <= 2^32 - 1. */
+ * d_ring and slot_stride 8-byte aligned, slot_stride >= 72 + frag_len, 1 <= frag_len <= 2^32 - 1.
+ * LAMPI_SEND_HDR_QUADRICS: slot k is a 128-byte envelope at d_ring + k*slot_stride.  Bytes [0, 72) come from tmpl
+ * (still 72 bytes) with the per-k fields above; the word @68 (dataElanAddr) is tmpl's plus k*frag_len mod 2^32
+ * (destination buffers frag_len apart, sendFrag.h:794); bytes [72, 124) are zero, then a fragment of 1..52 bytes
+ * is placed there; @64 and @124 follow the Quadrics table (an empty fragment keeps tmpl's word @64).  A fragment
+ * longer than 52 bytes goes to slot + 128 when slot_stride >= 128 + frag_len; with slot_stride == 128 (a bare
+ * envelope queue) nothing longer than 52 bytes is copied -- it is checksummed only, and with LAMPI_CSUM_NONE not
+ * read and its word @64 tmpl's.  Any other slot_stride with frag_len > 52 is rejected. */
 int lampi_msg_send_pack(const void *d_msg, size_t msg_len, size_t frag_len, void *d_ring, size_t slot_stride,
                         const lampi_send_hdr_fill *h_fill, int hdr_kind, int mode, void *stream);
 
@@ -557,6 +602,10 @@ int lampi_copy_to_app_batch(const lampi_recv_desc *d_descs, size_t n, const void
  *                      (lampi_header_check_batch with hdr_bytes 72, word_count 18, csum_offset 68)
  *   LAMPI_SEND_HDR_IB  CRC32: the word @68 == uicrc(H, 68);  SUM32: == uicsum(H, 68), unswapped
  *                      (lampi_header_compare_batch with crclen 68, csum_offset 68)
+ *   LAMPI_SEND_HDR_QUADRICS  H = the 128 bytes.  CRC32: uicrc(H, 128) == 0;  SUM32: the sum of words 0..31 ==
+ *                      2 x the word @124 (lampi_header_check_batch with hdr_bytes 128, word_count 32,
+ *                      csum_offset 124).  A payload of 1..52 bytes is read from header + 72: a flipped byte
+ *                      there fails the header, not the data.
  *   LAMPI_CSUM_NONE:   every header passes.
  * Per fragment i:
  *   header fails:  the fragment is dropped -- no payload byte is read, no application byte written;
@@ -577,7 +626,10 @@ int lampi_copy_to_app_batch(const lampi_recv_desc *d_descs, size_t n, const void
  * (d_hdrs and hdr_stride 4-byte aligned, hdr_stride >= 72); descriptor i is a lampi_recv_desc as for
  * lampi_copy_to_app_batch.  mode takes LAMPI_CSUM_ROWS_HINT as lampi_copy_to_app_batch does (and the library learns
  * the batches' shape the same way); LAMPI_CSUM_BY_BYTES is refused.  With LAMPI_CSUM_NONE no header is read and
- * d_hdrs may be NULL.  n == 0 returns 0 with both counts zeroed; n < 2^32. */
+ * d_hdrs may be NULL.  n == 0 returns 0 with both counts zeroed; n < 2^32.
+ * LAMPI_SEND_HDR_QUADRICS: hdr_stride >= 128 and d_hdrs is required in every mode (inline payloads live there);
+ * the length comes from the descriptor as for GM, and when 0 < length <= 52 frag is ignored: the payload is at
+ * header + 72. */
 int lampi_recv_unpack_batch(const lampi_recv_desc *d_descs, size_t n, const void *d_hdrs, size_t hdr_stride,
                             int hdr_kind, int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask,
                             uint32_t *d_data_mask, uint32_t *d_nbad /* 2 words */, int mode, void *stream);
@@ -591,7 +643,9 @@ int lampi_recv_unpack_batch(const lampi_recv_desc *d_descs, size_t n, const void
  * when Offset >= app_len (nothing copied, DataOK, BaseDesc.cc:312-316); then CopyToApp as above.  With
  * LAMPI_CSUM_NONE nothing is tested but the length.  Outputs are indexed by slot.  Where the destinations of two
  * slots overlap those bytes are unspecified; the verdicts stay per slot.  The schedule follows slot_stride
- * (mode takes no hint bits).  nslots == 0 returns 0 with both counts zeroed; nslots < 2^32. */
+ * (mode takes no hint bits).  nslots == 0 returns 0 with both counts zeroed; nslots < 2^32.
+ * LAMPI_SEND_HDR_QUADRICS: slot_stride >= 128; the payload is at slot + 72 when dataLength <= 52, otherwise at
+ * slot + 128, and a dataLength > 52 that exceeds slot_stride - 128 is malformed and dropped in every mode. */
 int lampi_msg_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride, int hdr_kind,
                           void *d_app, size_t app_len, uint64_t seq_offset0,
                           int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask, uint32_t *d_data_mask,

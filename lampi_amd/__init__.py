@@ -10,8 +10,8 @@ kernels for gfx950 behind the C ABI in include/lampi_csum.h (liblampi_csum.so).
 * :mod:`lampi_amd.device` -- batched device-resident checksums over torch tensors
   (imported lazily: it needs torch).
 """
-from ._lib import (CRC32, CRC_INITIAL_REGISTER, CRC_POLYNOMIAL, NONE, RECV_DATA_BAD, RECV_HDR_BAD,  # noqa: F401
-                   SUM32, FragDesc, lib)
+from ._lib import (CRC32, CRC_INITIAL_REGISTER, CRC_POLYNOMIAL, HDR_GM, HDR_IB, HDR_QUADRICS, NONE,  # noqa: F401
+                   RECV_DATA_BAD, RECV_HDR_BAD, SUM32, FragDesc, lib)
 from .memfunctions import (PartialState, PartialState64, bcopy_csum, bcopy_uicrc, bcopy_uicsum,  # noqa: F401
                            csum, header_checksum, uicrc, uicsum)
 

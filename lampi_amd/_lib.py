@@ -78,6 +78,7 @@ assert ctypes.sizeof(HostPiece) == 32
 
 HDR_GM = 0  # enum lampi_send_hdr_kind (include/lampi_csum.h)
 HDR_IB = 1
+HDR_QUADRICS = 3  # the 128-byte quadricsCtlHdr_t (2 is not a kind)
 RECV_DATA_BAD = -1  # LAMPI_RECV_DATA_BAD: CopyToApp's return for a corrupt payload
 RECV_HDR_BAD = -2  # LAMPI_RECV_HDR_BAD: the header failed its test (or is malformed), the fragment was dropped
 

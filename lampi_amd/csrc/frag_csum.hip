@@ -662,6 +662,96 @@ struct MsgRecvSource : RecvHdrBase {
     }
 };
 
+// ---- the Quadrics flavour of both steps (LAMPI_SEND_HDR_QUADRICS) --------------------------------------
+// quadricsCtlHdr_t's MESSAGE_DATA header (ref src/path/quadrics/header.h:71-87, :164-179) is 128 bytes: the fields
+// up to dataChecksum @64 where GM's and IB's are, then dataElanAddr @68, data[52] @72 and checksum @124.  A fragment
+// of at most CTLHDR_DATABYTES = 52 bytes travels inside the header (sendFrag.h:835-852, recvFrag.cc:159), so the
+// header checksum covers payload bytes: the send step is always the copy (or checksum) launch, its values in pooled
+// scratch, then one stamp launch over the headers as they then stand; the receive step always tests the headers in
+// a pass of their own (thirty-two table rounds per header are not repeated by every wave of a fragment).
+constexpr uint32_t kQHdrBytes = 128, kQHdrWords = 32, kQInline = 52, kQData = 72, kQHdrCsum = 124;
+
+// The send step per descriptor: CopySource's fragment, an inline one (max(copylen, csumlen) <= 52) copied to
+// header + 72 whatever its dst says; the checksum goes to out[f] for the stamp launch.
+struct QSendSource {
+    static constexpr bool kCopy = true;
+    static constexpr bool kPhase = false;
+    const lampi_copy_desc *d;
+    uint8_t *hdrs;  // header f at hdrs + f * hdr_stride
+    size_t hdr_stride;
+    __device__ FragInfo get(size_t f) const {
+        const lampi_copy_desc x = d[f];
+        const uint32_t len = x.copylen > x.csumlen ? x.copylen : x.csumlen;
+        uint8_t *dst = len <= kQInline ? hdrs + f * hdr_stride + kQData : (uint8_t *)(uintptr_t)x.dst;
+        return {(gbyte *)(uintptr_t)x.src, len, x.partial, dst, x.copylen};
+    }
+};
+// ... with checksumming off: only the copylen bytes are read (CopyOnlySource)
+struct QSendCopyOnlySource : QSendSource {
+    __device__ FragInfo get(size_t f) const {
+        const lampi_copy_desc x = d[f];
+        const uint32_t len = x.copylen > x.csumlen ? x.copylen : x.csumlen;
+        uint8_t *dst = len <= kQInline ? hdrs + f * hdr_stride + kQData : (uint8_t *)(uintptr_t)x.dst;
+        return {(gbyte *)(uintptr_t)x.src, x.copylen, 0u, dst, x.copylen};
+    }
+};
+
+// The receive step, descriptor form: RecvUnpackSource behind the pre-pass's record (always there with checksumming
+// on), the payload of a fragment of 1..52 bytes read from header + 72 (x.frag ignored).
+struct QRecvUnpackSource : RecvHdrBase {
+    const lampi_recv_desc *d;
+    __device__ gbyte *payload(size_t f, const lampi_recv_desc &x) const {
+        return x.length <= kQInline ? (gbyte *)(hdrs + f * hdr_stride + kQData) : (gbyte *)(uintptr_t)x.frag;
+    }
+    __device__ FragInfo get(size_t f) const {
+        const RecvHdrRec r = rec[f];
+        const lampi_recv_desc x = d[f];
+        const bool ok = r.ok != 0u;
+        const uint32_t c = ok ? RecvSource::to_copy(x) : 0u;
+        return {payload(f, x), c ? x.length : 0u, empty, (uint8_t *)(uintptr_t)x.app, c, c ? r.expected : 0u,
+                ok ? 0u : 1u};
+    }
+};
+// ... with checksumming off: every header passes; the inline payloads still live in the headers
+struct QRecvUnpackCopyOnlySource : QRecvUnpackSource {
+    __device__ FragInfo get(size_t f) const {
+        const lampi_recv_desc x = d[f];
+        const uint32_t c = RecvSource::to_copy(x);
+        return {payload(f, x), c, 0u, (uint8_t *)(uintptr_t)x.app, c, 0u};
+    }
+};
+
+// The ring form: MsgRecvSource over 128-byte envelopes, the payload at slot + 72 (dataLength <= 52) or slot + 128;
+// a dataLength > 52 that exceeds slot_stride - 128 is malformed (the pre-pass tests it too).  Its own twin with
+// checksumming off (no record then: the length alone is tested).
+struct QMsgRecvSource : RecvHdrBase {
+    uint8_t *app;
+    uint64_t app_len, seq0;
+    uint32_t max_len;  // slot_stride - 128
+    __device__ FragInfo get(size_t f) const {
+        const uint8_t *h = hdrs + f * hdr_stride;
+        const uint32_t len = *(guint *)(h + 4 * 5), so_lo = *(guint *)(h + 4 * 14), so_hi = *(guint *)(h + 4 * 15);
+        uint32_t e0 = 0u;
+        bool ok;
+        if (rec) {
+            const RecvHdrRec r = rec[f];
+            ok = r.ok != 0u;
+            e0 = r.expected;
+        } else {
+            ok = len <= kQInline || len <= max_len;
+        }
+        const uint64_t off = (((uint64_t)so_hi << 32) | so_lo) - seq0;
+        const uint64_t room = off >= app_len ? 0u : app_len - off;
+        const uint32_t c = ok ? (uint32_t)min((uint64_t)len, room) : 0u;
+        const uint32_t n = mode == LAMPI_CSUM_NONE ? c : (c ? len : 0u);
+        return {(gbyte *)(h + (len <= kQInline ? kQData : kQHdrBytes)), n, empty, c ? app + off : app, c, c ? e0 : 0u,
+                ok ? 0u : 1u};
+    }
+};
+template <class S>
+struct IsQuadricsRecv : std::integral_constant<bool, std::is_base_of<QRecvUnpackSource, S>::value ||
+                                                         std::is_same<S, QMsgRecvSource>::value> {};
+
 template <class S>
 struct IsRecvHdr : std::is_base_of<RecvHdrBase, S> {};
 // every receive source: emit asks it for the fragment's verdict
@@ -692,7 +782,9 @@ struct IsGroupRecv : std::false_type {};
 template <class S>
 struct IsGroupRecv<GroupSource<S>>
     : std::integral_constant<bool, std::is_same<S, RecvSource>::value || std::is_same<S, RecvUnpackSource>::value ||
-                                       std::is_same<S, MsgRecvSource>::value> {};
+                                       std::is_same<S, MsgRecvSource>::value ||
+                                       std::is_same<S, QRecvUnpackSource>::value ||
+                                       std::is_same<S, QMsgRecvSource>::value> {};
 
 // Byte-balanced descriptor batches (launch_crc_desc / launch_sum_desc for n <= kPlanMax): plan_kernel
 // cuts every fragment longer than the plan's window B into segments of at most B bytes and groups the
@@ -774,9 +866,15 @@ struct HasSegments : IsSeg<S> {};
 template <>
 struct HasSegments<RowSegSource> : std::true_type {};
 
+struct QMsgEnvelopeSource;  // (with the Quadrics stamp, below)
+
 // every kernel stores a fragment's checksum through this: receive sources also decide it
 template <class Src, class Acc>
 __device__ __forceinline__ void emit(const Src &src, Acc *out, size_t f, Acc v, const FragInfo &fi) {
+    if constexpr (std::is_same<Src, QMsgEnvelopeSource>::value) {  // no checksum: the fragment's envelope instead
+        src.envelope(f);
+        return;
+    }
     if constexpr (std::is_same<Src, HostOneSource>::value) {  // the host call's one result, then the signal
         out[f] = v;
         signal_host(src.sig, src.seq);
@@ -5374,6 +5472,10 @@ enum ShapeKind : int {
     kShapeSendPackNone = 5,     // ... with checksumming off
     kShapeRecvUnpack = 6,       // launch_recv_unpack, CRC and SUM
     kShapeRecvUnpackNone = 7,   // ... with checksumming off
+    kShapeQSendPack = 8,        // launch_send_pack over Quadrics headers (QSendSource), CRC and SUM
+    kShapeQSendPackNone = 9,    // ... with checksumming off
+    kShapeQRecvUnpack = 10,     // launch_recv_unpack over Quadrics headers, CRC and SUM
+    kShapeQRecvUnpackNone = 11, // ... with checksumming off
 };
 
 // What learn_shape found.  Every field but rows keeps its default when nothing was learned: the caller gave a
@@ -6179,6 +6281,177 @@ __global__ void __launch_bounds__(256) recv_hdr_test_kernel(const uint8_t *__res
     rec[i] = RecvHdrRec{ok ? 1u : 0u, w[16]};
 }
 
+// The words of a Quadrics header that its checksum covers, w[0..30], as the word @124 holds them
+// (BasePath_t::headerChecksum(H, 124, 32), quadrics/sendFrag.h:876-879): the register after thirty-one
+// slicing-by-4 rounds in the swapped domain -- bswap32(uicrc(H, 124)), so one more round over that word leaves
+// 0 -- or the sum of the words.
+template <class Tab>
+__device__ __forceinline__ uint32_t q_hdr_csum(const uint32_t *w, bool crc, const Tab &tab) {
+    uint32_t C = send_prefix_words(w, crc, tab);
+    if (!crc) {
+#pragma unroll
+        for (int i = 16; i < (int)kQHdrWords - 1; ++i) C += w[i];
+        return C;
+    }
+#pragma unroll
+    for (int i = 16; i < (int)kQHdrWords - 1; ++i) {
+        const uint32_t X = C ^ w[i];
+        C = tab(0u, X & 255u) ^ tab(1u, (X >> 8) & 255u) ^ tab(2u, (X >> 16) & 255u) ^ tab(3u, X >> 24);
+    }
+    return C;
+}
+
+// recv_hdr_test_kernel over 128-byte Quadrics headers (ref src/path/quadrics/path.cc:839-900): CRC uicrc(H, 128)
+// == 0 -- the register before the last round equals the word @124 --, SUM the sum of the 32 words == 2 x that
+// word.  max_len: the ring form's payload room after the envelope (a dataLength of more than 52 bytes beyond it is
+// malformed); 0xFFFFFFFF otherwise.
+__global__ void __launch_bounds__(256) qrecv_hdr_test_kernel(const uint8_t *__restrict__ hdrs, size_t stride,
+                                                             uint32_t n, int mode, uint32_t max_len,
+                                                             const uint32_t *__restrict__ img,
+                                                             RecvHdrRec *__restrict__ rec) {
+    __shared__ uint32_t S[1024];
+    if (mode == LAMPI_CSUM_CRC32) stage_slices(S, img);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *h = hdrs + (size_t)i * stride;
+    uint32_t w[kQHdrWords];
+#pragma unroll
+    for (int k = 0; k < (int)kQHdrWords; ++k) w[k] = *(guint *)(h + 4 * k);
+    const uint32_t c = q_hdr_csum(w, mode == LAMPI_CSUM_CRC32, SliceLds{S}), stored = w[kQHdrWords - 1];
+    const bool good = mode == LAMPI_CSUM_CRC32 ? c == stored : c + stored == stored + stored;
+    const uint32_t len = w[kRecvLenWord];
+    const bool ok = good && (len <= kQInline || len <= max_len);
+    rec[i] = RecvHdrRec{ok ? 1u : 0u, w[16]};
+}
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) u32x2 gwu32x2;
+
+// Slot i's whole Quadrics envelope built in registers and stored once, as sixteen 8-byte stores (h 8-byte aligned):
+// fill.tmpl's 72 bytes with the fields of fragment i as send_stamp_kernel<true> gives them, dataElanAddr @68 = tmpl's
+// + i * frag_len (destination buffers frag_len apart, ref src/path/quadrics/sendFrag.h:794), data[] zero with an
+// inline fragment's payload (at most 52 bytes of the message) loaded here, then the words @64 and @124 of the table
+// (vals: the fragments' checksums, unused with checksumming off; bare: a longer fragment is not copied).
+template <class Tab>
+__device__ __forceinline__ void q_build_envelope(uint8_t *h, uint32_t i, const SendFill &fill, const uint8_t *base,
+                                                 size_t msg_len, size_t frag_len, bool bare, int mode,
+                                                 const uint32_t *vals, const Tab &tab) {
+    const bool none = mode == LAMPI_CSUM_NONE;
+    uint32_t w[kQHdrWords];
+    const size_t off = (size_t)i * frag_len, rem = msg_len > off ? msg_len - off : 0;
+    const uint32_t len = (uint32_t)(rem < frag_len ? rem : frag_len);
+#pragma unroll
+    for (int k = 0; k < (int)(kSendHdrBytes / 4); ++k) w[k] = fill.tmpl[k];
+#pragma unroll
+    for (int k = (int)(kSendHdrBytes / 4); k < (int)kQHdrWords; ++k) w[k] = 0u;
+    const uint64_t seq = fill.frag_seq0 + i * fill.frag_seq_step, ptr = fill.desc_ptr0 + i * fill.desc_ptr_stride,
+                   so = fill.seq_offset0 + (uint64_t)off;
+    w[5] = len;
+    w[8] = (uint32_t)seq;
+    w[9] = (uint32_t)(seq >> 32);
+    w[12] = (uint32_t)ptr;
+    w[13] = (uint32_t)(ptr >> 32);
+    w[14] = (uint32_t)so;
+    w[15] = (uint32_t)(so >> 32);
+    w[17] += (uint32_t)off;  // (i * frag_len mod 2^32)
+    const bool inl = len != 0u && len <= kQInline;
+    if (inl) {  // whole words where the source is on the word grid, the rest byte by byte
+        gbyte *p = (gbyte *)(base + off);
+        const bool al = ((uintptr_t)p & 3u) == 0;
+#pragma unroll
+        for (int k = 0; k < (int)(kQInline / 4); ++k) {
+            const uint32_t b0 = 4u * (uint32_t)k;
+            uint32_t v = 0u;
+            if (al && b0 + 4u <= len) {
+                v = *(guint *)(p + b0);
+            } else {
+#pragma unroll
+                for (uint32_t b = 0; b < 4u; ++b)
+                    if (b0 + b < len) v |= (uint32_t)p[b0 + b] << (8u * b);
+            }
+            w[kQData / 4 + k] = v;
+        }
+    }
+    if (none) {
+        if (inl || (len != 0u && !bare)) w[16] = 0u;
+    } else if (len != 0u) {
+        w[16] = vals[i];
+    }
+    w[kQHdrWords - 1] = none ? 0u : q_hdr_csum(w, mode == LAMPI_CSUM_CRC32, tab);
+#pragma unroll
+    for (int k = 0; k < (int)kQHdrWords / 2; ++k) *(gwu32x2 *)(h + 8 * k) = u32x2{w[2 * k], w[2 * k + 1]};
+}
+
+// The message form with checksumming off and fragments of 53 bytes .. one row (not the short-lived 4 KiB rows'
+// lengths): MsgCopySource's copy on sum_copy_wg_kernel -- the schedule launch_msg_bcopy picks there -- whose emit
+// builds the fragment's envelope instead of storing a sum.  Nothing in an envelope depends on the payload then (both
+// checksum words are constants), so no second launch has to follow the copies.  262,144 x 2,048 bytes: 0.1865 ms
+// with the stamp launch (profiles/r09/quadrics_ab_none2l.txt), 0.1850 ms so (profiles/r09/quadrics_ab.txt) --
+// lampi_msg_bcopy_strided, which writes no header, 0.1738: what remains is the envelope bytes.
+// A last fragment of 1..52 bytes is not copied here: the emitting thread loads it (q_build_envelope).
+namespace {
+struct QMsgEnvelopeSource {
+    static constexpr bool kCopy = true;
+    static constexpr bool kPhase = false;
+    const uint8_t *base;
+    size_t msg_len;
+    size_t frag_len;
+    uint8_t *ring;  // slot f at ring + f * slot_stride
+    size_t slot_stride;
+    SendFill fill;
+    __device__ FragInfo get(size_t f) const {
+        const size_t off = f * frag_len, rem = msg_len - off;
+        const uint32_t len = (uint32_t)(rem < frag_len ? rem : frag_len);
+        if (len <= kQInline) return {(gbyte *)(base + off), 0u, 0u, nullptr, 0u};
+        return {(gbyte *)(base + off), len, 0u, ring + f * slot_stride + kQHdrBytes, len};
+    }
+    __device__ void envelope(size_t f) const {
+        q_build_envelope(ring + f * slot_stride, (uint32_t)f, fill, base, msg_len, frag_len, false, LAMPI_CSUM_NONE,
+                         nullptr, SliceGlobal{nullptr});
+    }
+};
+}  // namespace
+
+// The Quadrics stamp (ref src/path/quadrics/sendFrag.h:766-880, :970-986), the launch after the one that left the
+// fragments' checksums in vals and the descriptor form's inline payloads in the headers: one thread per header on
+// the LDS slice tables, as send_stamp_kernel.  len = the fragment's max(copylen, csumlen):
+//   @64   checksumming on: vals[i], untouched when len == 0;  off: 0 when bytes were copied, else untouched
+//   @124  headerChecksum(H, 124, 32) over the header as it then stands (q_hdr_csum);  off: 0 (:768)
+// kBuild (lampi_msg_send_pack): q_build_envelope instead.
+template <bool kBuild>
+__global__ void __launch_bounds__(256) qsend_stamp_kernel(uint8_t *hdrs, size_t stride, uint32_t n,
+                                                          const uint32_t *__restrict__ vals,
+                                                          const lampi_copy_desc *__restrict__ d, const SendFill fill,
+                                                          const uint8_t *__restrict__ base, size_t msg_len,
+                                                          size_t frag_len, int bare, int mode,
+                                                          const uint32_t *__restrict__ img) {
+    __shared__ uint32_t S[1024];
+    if (mode == LAMPI_CSUM_CRC32) stage_slices(S, img);
+    const SliceLds tab{S};
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint8_t *h = hdrs + (size_t)i * stride;
+    if constexpr (kBuild) {
+        q_build_envelope(h, i, fill, base, msg_len, frag_len, bare != 0, mode, vals, tab);
+    } else {
+        const lampi_copy_desc x = d[i];
+        gwuint *w64 = (gwuint *)(h + kSendDataCsum), *w124 = (gwuint *)(h + kQHdrCsum);
+        uint32_t w[kQHdrWords];
+        if (mode == LAMPI_CSUM_NONE) {
+            if (x.copylen != 0u) *w64 = 0u;
+            *w124 = 0u;
+            return;
+        }
+#pragma unroll
+        for (int k = 0; k < (int)kQHdrWords - 1; ++k) w[k] = *(guint *)(h + 4 * k);
+        if ((x.copylen | x.csumlen) != 0u) {
+            w[16] = vals[i];
+            *w64 = w[16];
+        }
+        *w124 = q_hdr_csum(w, mode == LAMPI_CSUM_CRC32, tab);
+    }
+}
+
 // The schedules of launch_copy_to_app over a receive-step source (Src: RecvUnpackSource or MsgRecvSource, Co its twin
 // with checksumming off).  sh.pairs: fragments of at most 2 KiB (CRC two to a wave, SUM / NONE one wave each).
 // Where the header is tested (profiles/r08/recv_unpack_ab.txt): inside get() -- the wave or
@@ -6206,14 +6479,22 @@ static hipError_t launch_recv_hdr(Src src, size_t n, uint32_t *csum, const uint3
     }
     // (checksumming off: the descriptor form reads no header; the ring form tests the length alone, in get())
     const bool ring = max_len != 0xFFFFFFFFu;
-    const bool pre = prepass == 2 ? !none || ring : prepass == 1 && !none && (groups || (crc && sh.pairs));
+    // (Quadrics sources: always with checksumming on, their get() has no header test of its own)
+    constexpr bool quadrics = IsQuadricsRecv<Src>::value;
+    const bool pre = quadrics       ? !none
+                     : prepass == 2 ? !none || ring
+                                    : prepass == 1 && !none && (groups || (crc && sh.pairs));
     RecvHdrRec *rec = nullptr;
     bool pooled = false;
     if (pre) {
         hipError_t e = stream_vals(s, 2 * n, (uint32_t **)&rec, &pooled);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(recv_hdr_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.hdrs,
-                           src.hdr_stride, (uint32_t)n, src.kind, mode, max_len, img, rec);
+        if constexpr (quadrics)
+            hipLaunchKernelGGL(qrecv_hdr_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.hdrs,
+                               src.hdr_stride, (uint32_t)n, mode, max_len, img, rec);
+        else
+            hipLaunchKernelGGL(recv_hdr_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.hdrs,
+                               src.hdr_stride, (uint32_t)n, src.kind, mode, max_len, img, rec);
         e = hipGetLastError();
         if (e != hipSuccess) return scratch_done(s, rec, pooled, e);
         src.rec = rec;
@@ -6251,35 +6532,46 @@ hipError_t launch_recv_unpack(const lampi_recv_desc *d, size_t n, const uint8_t 
                               const uint32_t *img, hipStream_t s, uint32_t rows_hint) {
     if (n == 0) return hipMemsetAsync(nbad, 0, 2 * sizeof(uint32_t), s);
     if (!img) return hipErrorInvalidValue;
-    RecvUnpackSource src;
-    fill_recv_hdr_base(src, hdrs, hdr_stride, kind, mode, img, copied, hmask, dmask, nbad);
-    src.d = d;
+    // (Quadrics: the same census over the descriptors -- the lengths are theirs -- in records of its own kinds)
+    const bool quadrics = kind == LAMPI_SEND_HDR_QUADRICS;
     LearnedShape sh;
     if (mode == LAMPI_CSUM_NONE) {
         RecvCopyOnlySource shape;
         static_cast<RecvSource &>(shape) = RecvSource{d, 0u, nullptr, 0, copied, dmask, nbad};
-        sh = learn_shape(shape, n, s, kShapeRecvUnpackNone, rows_hint, shape_opts(mode));
+        sh = learn_shape(shape, n, s, quadrics ? kShapeQRecvUnpackNone : kShapeRecvUnpackNone, rows_hint,
+                         shape_opts(mode));
     } else {
-        const RecvSource shape{d, src.empty, hdrs + kSendDataCsum, hdr_stride, copied, dmask, nbad};
-        sh = learn_shape(shape, n, s, kShapeRecvUnpack, rows_hint, shape_opts(mode));
+        const RecvSource shape{d, mode == LAMPI_CSUM_CRC32 ? 0xFFFFFFFFu : 0u, hdrs + kSendDataCsum, hdr_stride,
+                               copied, dmask, nbad};
+        sh = learn_shape(shape, n, s, quadrics ? kShapeQRecvUnpack : kShapeRecvUnpack, rows_hint, shape_opts(mode));
     }
+    if (quadrics) {
+        QRecvUnpackSource src;
+        fill_recv_hdr_base(src, hdrs, hdr_stride, kind, mode, img, copied, hmask, dmask, nbad);
+        src.d = d;
+        return launch_recv_hdr<QRecvUnpackCopyOnlySource>(src, n, csum, img, s, sh, 0xFFFFFFFFu);
+    }
+    RecvUnpackSource src;
+    fill_recv_hdr_base(src, hdrs, hdr_stride, kind, mode, img, copied, hmask, dmask, nbad);
+    src.d = d;
     return launch_recv_hdr<RecvUnpackCopyOnlySource>(src, n, csum, img, s, sh, 0xFFFFFFFFu);
 }
 
 // The ring form: nothing to learn, the slot size says what the fragments can be -- at most 2 KiB: pairs; otherwise
 // the slot's rows as the hint where a learned hint would be taken (kShapeRows / kShapeRowsSum rows or more).
 // MsgRecvSource is its own twin with checksumming off (get() reads the mode: the length still has to be tested).
-hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slot_stride, int kind, uint8_t *app,
-                                  size_t app_len, uint64_t seq0, int64_t *copied, uint32_t *csum, uint32_t *hmask,
-                                  uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s) {
-    if (nslots == 0) return hipMemsetAsync(nbad, 0, 2 * sizeof(uint32_t), s);
-    if (!img) return hipErrorInvalidValue;
-    MsgRecvSource src;
+// Src: MsgRecvSource (hdr_bytes 72) or QMsgRecvSource (128: the payload room is what follows the envelope).
+template <class Src>
+static hipError_t msg_recv_unpack_as(uint32_t hdr_bytes, const uint8_t *ring, size_t nslots, size_t slot_stride,
+                                     int kind, uint8_t *app, size_t app_len, uint64_t seq0, int64_t *copied,
+                                     uint32_t *csum, uint32_t *hmask, uint32_t *dmask, uint32_t *nbad, int mode,
+                                     const uint32_t *img, hipStream_t s) {
+    Src src;
     fill_recv_hdr_base(src, ring, slot_stride, kind, mode, img, copied, hmask, dmask, nbad);
     src.app = app;
     src.app_len = app_len;
     src.seq0 = seq0;
-    const size_t room = std::min<size_t>(slot_stride - kSendHdrBytes, 0xFFFFFFFEull);
+    const size_t room = std::min<size_t>(slot_stride - hdr_bytes, 0xFFFFFFFEull);
     src.max_len = (uint32_t)room;
     const bool crc = mode == LAMPI_CSUM_CRC32;
     bool pairs = room <= (size_t)kRowBytes / 2;
@@ -6291,7 +6583,19 @@ hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slo
     const size_t R = (room + kRowBytes - 1) / kRowBytes;
     LearnedShape sh{R >= shape_opts(mode).min_rows ? (uint32_t)std::min<size_t>(R, 4095) : 1u};
     sh.pairs = pairs;  // (nhalf_dev stays null: no census record to correct)
-    return launch_recv_hdr<MsgRecvSource>(src, nslots, csum, img, s, sh, src.max_len);
+    return launch_recv_hdr<Src>(src, nslots, csum, img, s, sh, src.max_len);
+}
+
+hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slot_stride, int kind, uint8_t *app,
+                                  size_t app_len, uint64_t seq0, int64_t *copied, uint32_t *csum, uint32_t *hmask,
+                                  uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s) {
+    if (nslots == 0) return hipMemsetAsync(nbad, 0, 2 * sizeof(uint32_t), s);
+    if (!img) return hipErrorInvalidValue;
+    if (kind == LAMPI_SEND_HDR_QUADRICS)
+        return msg_recv_unpack_as<QMsgRecvSource>(kQHdrBytes, ring, nslots, slot_stride, kind, app, app_len, seq0, copied,
+                                                  csum, hmask, dmask, nbad, mode, img, s);
+    return msg_recv_unpack_as<MsgRecvSource>(kSendHdrBytes, ring, nslots, slot_stride, kind, app, app_len, seq0, copied,
+                                             csum, hmask, dmask, nbad, mode, img, s);
 }
 
 hipError_t launch_sum64_desc(const lampi_frag_desc *d, size_t n, uint64_t *out, bool phased, hipStream_t s) {
@@ -6712,10 +7016,39 @@ hipError_t launch_scatter_u32(const uint32_t *vals, size_t n, uint8_t *dst, size
 //   from the global tables -- 16,384 x 65,456 bytes 0.3999 ms fused, 0.3837 ms in two launches (A 0.3899).
 // A/B knob LAMPI_SEND_FUSED: 0 = every batch through launch_bcopy_desc into pooled scratch, then send_stamp_kernel
 // (the message form's route); 1 = every batch fused, the pair kernel and the CRC join too.
+// The Quadrics kind: always two launches, because an inline payload lands in bytes the header checksum reads --
+// launch_fused_copy over QSendSource with the checksums in pooled scratch (checksumming off: the plain copy
+// schedules over QSendCopyOnlySource), then qsend_stamp_kernel.  Shapes are learned in records of its own kinds.
+static hipError_t launch_qsend_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, size_t hdr_stride, int mode,
+                                    const uint32_t *img, hipStream_t s, uint32_t rows_hint) {
+    uint32_t *vals = nullptr;
+    bool pooled = false;
+    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    if (e != hipSuccess) return e;
+    const QSendSource src{d, hdrs, hdr_stride};
+    if (mode == LAMPI_CSUM_NONE) {
+        QSendCopyOnlySource co;
+        static_cast<QSendSource &>(co) = src;
+        const LearnedShape sh = learn_shape(co, n, s, kShapeQSendPackNone, rows_hint, shape_opts(mode));
+        e = launch_sum_copy_groups(co, n, vals, s, sh.rows, sh.pairs);
+    } else {
+        const LearnedShape sh = learn_shape(src, n, s, kShapeQSendPack, rows_hint, shape_opts(mode));
+        e = launch_fused_copy(src, mode == LAMPI_CSUM_CRC32, n, img, vals, s, sh);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(qsend_stamp_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs, hdr_stride,
+                           (uint32_t)n, (const uint32_t *)vals, d, SendFill{}, (const uint8_t *)nullptr, (size_t)0,
+                           (size_t)0, 0, mode, img);
+        e = hipGetLastError();
+    }
+    return scratch_done(s, vals, pooled, e);
+}
+
 hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, size_t hdr_stride, int kind, int mode,
                             const uint32_t *img, hipStream_t s, uint32_t rows_hint) {
     if (n == 0) return hipSuccess;
     if (!img) return hipErrorInvalidValue;
+    if (kind == LAMPI_SEND_HDR_QUADRICS) return launch_qsend_pack(d, n, hdrs, hdr_stride, mode, img, s, rows_hint);
     static const int fused = [] {  // 0: two launches, 1: as measured, 2: fused everywhere
         const char *e = LAMPI_AB_ENV("LAMPI_SEND_FUSED");
         return !e ? 1 : e[0] == '0' ? 0 : 2;
@@ -6756,9 +7089,64 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
 // several of which have no single owner of a fragment (sum_copy_row_kernel's atomic row sums, the two-pass CRC
 // copies, the sum_row4k rows) -- with the checksums in pooled scratch, then one send_stamp_kernel<true> that writes
 // the headers.  Checksumming off: the SUM copy schedules, their sums unused (as lampi_msg_bcopy_strided).
+// The read-only checksums of a message's fragments (lampi_msg_csum's dispatch): the fastest kernels there are for
+// fragments that are not copied.
+static hipError_t msg_csum_readonly(const uint8_t *base, size_t msg_len, size_t frag_len, size_t n, uint32_t *out,
+                                    int mode, const uint32_t *img, int grid, hipStream_t s) {
+    if (mode == LAMPI_CSUM_SUM32) return launch_sum_msg(base, msg_len, frag_len, n, out, img, grid, s);
+    const bool regular = msg_len != 0 && frag_len % kRowBytes == 0 && msg_len % frag_len == 0 &&
+                         regular_msg_frag(frag_len, false) && ((uintptr_t)base & 15u) == 0 &&
+                         !crc_light_msg(frag_len, msg_len);
+    if (regular) return launch_crc_regular(base, n, frag_len, kCrcInit, out, img, grid, s);
+    return launch_crc_msg(base, msg_len, frag_len, kCrcInit, n, out, img, grid, s);
+}
+
+// The Quadrics kind of the message form: the first launch leaves the fragments' checksums in vals, the stamp builds
+// the envelopes and places inline payloads (one exception with checksumming off: QMsgEnvelopeSource).
+//   frag_len <= 52 (every fragment inline) or slot_stride == 128 (a bare envelope queue, longer fragments
+//   checksummed only): the read-only message kernels, nothing with checksumming off;
+//   otherwise launch_msg_bcopy into slot + 128 for the fragments longer than 52 bytes (checksumming off: the SUM
+//   copy schedules, their sums unused, as lampi_msg_bcopy_strided) -- a last fragment of 1..52 bytes is inline: it
+//   is left out of the copy and checksummed by a read-only launch of its own.
+static hipError_t launch_qmsg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
+                                        size_t slot_stride, const SendFill &f, size_t n, int mode, const uint32_t *img,
+                                        int grid, hipStream_t s) {
+    uint32_t *vals = nullptr;
+    bool pooled = false;
+    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    if (e != hipSuccess) return e;
+    const bool none = mode == LAMPI_CSUM_NONE, bare = slot_stride == kQHdrBytes && frag_len > kQInline;
+    // checksumming off, fragments of 53 bytes .. one row that launch_msg_bcopy would give a workgroup each: the same
+    // copy, the envelopes from its emit, one launch
+    if (none && !bare && msg_len != 0 && frag_len > kQInline && frag_len < (size_t)kRowBytes && !row4k_len(frag_len)) {
+        launch_sum_copy(QMsgEnvelopeSource{base, msg_len, frag_len, ring, slot_stride, f}, n, vals, s);
+        return scratch_done(s, vals, pooled, hipGetLastError());
+    }
+    if (msg_len != 0) {
+        if (frag_len <= kQInline || bare) {
+            if (!none) e = msg_csum_readonly(base, msg_len, frag_len, n, vals, mode, img, grid, s);
+        } else {
+            const size_t last = msg_len - (n - 1) * frag_len;
+            const size_t nfull = last <= kQInline ? n - 1 : n;
+            if (nfull)
+                e = launch_msg_bcopy(base, std::min(msg_len, nfull * frag_len), frag_len, kCrcInit, ring + kQHdrBytes,
+                                     slot_stride, nfull, vals, none ? LAMPI_CSUM_SUM32 : mode, img, s);
+            if (e == hipSuccess && nfull < n && !none)
+                e = msg_csum_readonly(base + nfull * frag_len, last, last, 1, vals + nfull, mode, img, grid, s);
+        }
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(qsend_stamp_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ring, slot_stride,
+                           (uint32_t)n, (const uint32_t *)vals, (const lampi_copy_desc *)nullptr, f, base, msg_len,
+                           frag_len, bare ? 1 : 0, mode, img);
+        e = hipGetLastError();
+    }
+    return scratch_done(s, vals, pooled, e);
+}
+
 hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
                                 size_t slot_stride, const lampi_send_hdr_fill &fill, size_t n, int kind, int mode,
-                                const uint32_t *img, hipStream_t s) {
+                                const uint32_t *img, hipStream_t s, int grid) {
     if (n == 0) return hipSuccess;
     if (!img) return hipErrorInvalidValue;
     SendFill f;
@@ -6769,6 +7157,8 @@ hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag
     f.desc_ptr0 = fill.desc_ptr0;
     f.desc_ptr_stride = fill.desc_ptr_stride;
     f.seq_offset0 = fill.seq_offset0;
+    if (kind == LAMPI_SEND_HDR_QUADRICS)
+        return launch_qmsg_send_pack(base, msg_len, frag_len, ring, slot_stride, f, n, mode, img, grid, s);
     uint32_t *vals = nullptr;
     bool pooled = false;
     hipError_t e = stream_vals(s, n, &vals, &pooled);

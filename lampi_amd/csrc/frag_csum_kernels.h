@@ -64,9 +64,14 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
                             const uint32_t *img, hipStream_t s, uint32_t rows_hint = 1);
 // ... and of launch_msg_bcopy into ring + 72 + k*slot_stride, followed by one launch that builds slot k's whole
 // header from `fill` (host memory, read here) and stamps it.
+// kind LAMPI_SEND_HDR_QUADRICS (both forms): 128-byte headers, a fragment of at most 52 bytes placed in the header
+// at +72, longer ones at ring + 128 + k*slot_stride or, with slot_stride == 128, checksummed only by the read-only
+// message kernels (grid = crc_grid(device), used by this kind alone); always the copy or checksum launch, then one
+// stamp launch (ref src/path/quadrics/sendFrag.h:766-880) -- except the message form with checksumming off and
+// fragments of 53 bytes .. one row, whose copy workgroups write the envelopes themselves.
 hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
                                 size_t slot_stride, const lampi_send_hdr_fill &fill, size_t n, int kind, int mode,
-                                const uint32_t *img, hipStream_t s);
+                                const uint32_t *img, hipStream_t s, int grid = 0);
 // RecvDesc_t::CopyToApp per descriptor (copy min(length, app_len), checksum length, verify).
 hipError_t launch_copy_to_app(const lampi_recv_desc *d, size_t n, const uint8_t *expected, size_t exp_stride,
                               int64_t *copied, uint32_t *csum, uint32_t *mask, uint32_t *nbad, int mode,
@@ -80,6 +85,9 @@ hipError_t launch_recv_unpack(const lampi_recv_desc *d, size_t n, const uint8_t 
                               const uint32_t *img, hipStream_t s, uint32_t rows_hint = 1);
 // ... and with every field taken from the headers of a ring of header + payload slots: dataLength @20 (at most
 // slot_stride - 72), destination app + (dataSeqOffset @56 - seq0), room app_len less that offset.
+// kind LAMPI_SEND_HDR_QUADRICS (both forms): 128-byte headers tested by a pass of their own (uicrc(H, 128) == 0 /
+// the 32 words' sum == 2 x the word @124; hdrs is read in every mode), a payload of 1..52 bytes read from its
+// header at +72, a longer one from the descriptor's frag / slot + 128 (ref src/path/quadrics/recvFrag.cc:150-160).
 hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slot_stride, int kind, uint8_t *app,
                                   size_t app_len, uint64_t seq0, int64_t *copied, uint32_t *csum, uint32_t *hmask,
                                   uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s);

@@ -100,6 +100,13 @@ namespace {
 
 int to_int(hipError_t e) { return (int)e; }
 
+// enum lampi_send_hdr_kind: the value 2 is not a kind
+bool hdr_kind_ok(int kind) {
+    return kind == LAMPI_SEND_HDR_GM || kind == LAMPI_SEND_HDR_IB || kind == LAMPI_SEND_HDR_QUADRICS;
+}
+// the data header of a kind: gmHeaderData / ibDataHdr_t 72 bytes, quadricsCtlHdr_t 128
+size_t data_hdr_bytes(int kind) { return kind == LAMPI_SEND_HDR_QUADRICS ? 128 : 72; }
+
 // ------------------------------------------------------------------ host-path context
 
 #define LAMPI_CHECK(call)                      \
@@ -700,9 +707,11 @@ int lampi_recv_unpack_batch(const lampi_recv_desc *d_descs, size_t n, const void
     mode &= ~LAMPI_CSUM_ROWS_HINT_MASK;  // (LAMPI_CSUM_BY_BYTES stays in and is refused)
     if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
         return to_int(hipErrorInvalidValue);
-    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return to_int(hipErrorInvalidValue);
-    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < 72) return to_int(hipErrorInvalidValue);
-    const bool check = mode != LAMPI_CSUM_NONE;  // (checksumming off: no header is read)
+    if (!hdr_kind_ok(hdr_kind)) return to_int(hipErrorInvalidValue);
+    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < data_hdr_bytes(hdr_kind))
+        return to_int(hipErrorInvalidValue);
+    // (checksumming off: no header is read -- except Quadrics', which hold the inline payloads)
+    const bool check = mode != LAMPI_CSUM_NONE || hdr_kind == LAMPI_SEND_HDR_QUADRICS;
     if (!d_nbad || n > 0xFFFFFFFFull ||
         (n && (!d_descs || (check && !d_hdrs) || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask)))
         return to_int(hipErrorInvalidValue);
@@ -723,8 +732,9 @@ int lampi_msg_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride,
                           uint32_t *d_hdr_mask, uint32_t *d_data_mask, uint32_t *d_nbad, int mode, void *stream) {
     if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
         return to_int(hipErrorInvalidValue);  // (no hint bits: the slot size says the shape)
-    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return to_int(hipErrorInvalidValue);
-    if (((uintptr_t)d_ring & 7u) || (slot_stride & 7u) || slot_stride < 72) return to_int(hipErrorInvalidValue);
+    if (!hdr_kind_ok(hdr_kind)) return to_int(hipErrorInvalidValue);
+    if (((uintptr_t)d_ring & 7u) || (slot_stride & 7u) || slot_stride < data_hdr_bytes(hdr_kind))
+        return to_int(hipErrorInvalidValue);
     if (!d_nbad || nslots > 0xFFFFFFFFull || (app_len && !d_app) ||
         (nslots && (!d_ring || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask)))
         return to_int(hipErrorInvalidValue);
@@ -793,8 +803,9 @@ int lampi_send_pack_batch(const lampi_copy_desc *d_descs, size_t n, void *d_hdrs
     const int base_mode = mode & ~LAMPI_CSUM_ROWS_HINT_MASK;
     if (base_mode != LAMPI_CSUM_CRC32 && base_mode != LAMPI_CSUM_SUM32 && base_mode != LAMPI_CSUM_NONE)
         return to_int(hipErrorInvalidValue);
-    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return to_int(hipErrorInvalidValue);
-    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < 72) return to_int(hipErrorInvalidValue);
+    if (!hdr_kind_ok(hdr_kind)) return to_int(hipErrorInvalidValue);
+    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < data_hdr_bytes(hdr_kind))
+        return to_int(hipErrorInvalidValue);
     // GM with checksumming off writes no header word (gm/sendFrag.cc:153-155, :219): the headers may be absent
     const bool no_hdrs = base_mode == LAMPI_CSUM_NONE && hdr_kind == LAMPI_SEND_HDR_GM;
     if (n == 0) return 0;
@@ -813,10 +824,18 @@ int lampi_msg_send_pack(const void *d_msg, size_t msg_len, size_t frag_len, void
                         const lampi_send_hdr_fill *h_fill, int hdr_kind, int mode, void *stream) {
     if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
         return to_int(hipErrorInvalidValue);
-    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return to_int(hipErrorInvalidValue);
+    if (!hdr_kind_ok(hdr_kind)) return to_int(hipErrorInvalidValue);
+    const size_t hb = data_hdr_bytes(hdr_kind);
     if (frag_len == 0 || frag_len > 0xFFFFFFFFull || !d_ring || !h_fill || ((uintptr_t)d_ring & 7u) ||
-        (slot_stride & 7u) || slot_stride < 72 || slot_stride - 72 < frag_len || (msg_len && !d_msg))
+        (slot_stride & 7u) || slot_stride < hb || (msg_len && !d_msg))
         return to_int(hipErrorInvalidValue);
+    if (hdr_kind == LAMPI_SEND_HDR_QUADRICS) {
+        // fragments of at most 52 bytes travel in the envelope; longer ones need room after it, or a bare envelope
+        // queue (slot_stride == 128: checksummed, not copied)
+        if (frag_len > 52 && slot_stride != hb && slot_stride - hb < frag_len) return to_int(hipErrorInvalidValue);
+    } else if (slot_stride - hb < frag_len) {
+        return to_int(hipErrorInvalidValue);
+    }
     // a zero-length message is one empty fragment (the path layer still sends a header)
     const size_t n = msg_len ? (msg_len + frag_len - 1) / frag_len : 1;
     if (n > 0xFFFFFFFFull) return to_int(hipErrorInvalidValue);
@@ -827,7 +846,7 @@ int lampi_msg_send_pack(const void *d_msg, size_t msg_len, size_t frag_len, void
     e = device_tables(dev, &img);
     if (e != hipSuccess) return to_int(e);
     return to_int(launch_msg_send_pack((const uint8_t *)d_msg, msg_len, frag_len, (uint8_t *)d_ring, slot_stride, *h_fill,
-                                       n, hdr_kind, mode, img, (hipStream_t)stream));
+                                       n, hdr_kind, mode, img, (hipStream_t)stream, crc_grid(dev)));
 }
 
 int lampi_chain_csum_batch_strided(const lampi_copy_desc *d_pieces, size_t npieces, const uint32_t *d_first,

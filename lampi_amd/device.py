@@ -9,10 +9,10 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._lib import (BY_BYTES, CRC32, CRC_INITIAL_REGISTER, HDR_GM, HDR_IB, NONE, RECV_DATA_BAD, RECV_HDR_BAD, SUM32,
-                   SendHdrFill, check, lib, rows_hint_bits)
+from ._lib import (BY_BYTES, CRC32, CRC_INITIAL_REGISTER, HDR_GM, HDR_IB, HDR_QUADRICS, NONE, RECV_DATA_BAD, RECV_HDR_BAD,
+                   SUM32, SendHdrFill, check, lib, rows_hint_bits)
 
-__all__ = ["CRC32", "SUM32", "NONE", "HDR_GM", "HDR_IB", "RECV_DATA_BAD", "RECV_HDR_BAD", "recv_unpack_batch", "msg_recv_unpack",
+__all__ = ["CRC32", "SUM32", "NONE", "HDR_GM", "HDR_IB", "HDR_QUADRICS", "RECV_DATA_BAD", "RECV_HDR_BAD", "recv_unpack_batch", "msg_recv_unpack",
            "send_pack_batch", "msg_send_pack","chain_copy_to_app_batch", "frag_bcopy_batch_strided", "msg_bcopy_strided",
            "chain_csum_batch_strided", "header_csum_batch_strided", "frag_csum_batch", "diag_frag_csum_batch_per_wave", "frag_csum64_batch", "frag_bcopy_batch", "msg_bcopy", "msg_csum", "fill_stream", "fill_stream_frags",
            "make_descs", "make_copy_descs", "as_u32", "chain_csum_batch", "header_csum_batch", "header_check_batch", "check_data_batch",
@@ -265,6 +265,13 @@ def msg_bcopy_strided(msg: torch.Tensor, frag_len: int, dst: torch.Tensor, dst_s
 
 
 SEND_HDR_BYTES = 72  # gmHeaderData / ibDataHdr_t (dataChecksum @64, checksum @68)
+QUADRICS_HDR_BYTES = 128  # quadricsCtlHdr_t (dataChecksum @64, dataElanAddr @68, data[52] @72, checksum @124)
+QUADRICS_INLINE_BYTES = 52  # CTLHDR_DATABYTES: a fragment of at most this many bytes travels inside the header
+
+
+def hdr_bytes(kind: int) -> int:
+    """The data header's length for ``kind``: 72 (HDR_GM, HDR_IB) or 128 (HDR_QUADRICS)."""
+    return QUADRICS_HDR_BYTES if kind == HDR_QUADRICS else SEND_HDR_BYTES
 
 
 def send_pack_batch(descs: torch.Tensor, hdrs: torch.Tensor | None, hdr_stride: int, offset: int = 0,
@@ -273,7 +280,12 @@ def send_pack_batch(descs: torch.Tensor, hdrs: torch.Tensor | None, hdr_stride: 
     """The send step in one call (src/path/gm/sendFrag.cc:143-226, src/path/ib/sendFrag.cc:289-320): every
     ``lampi_copy_desc`` copied with its checksum fused, and header i -- 72 bytes at byte offset + i*hdr_stride of
     ``hdrs``, bytes [0, 64) already filled -- given dataChecksum @64 and the header checksum @68 of ``kind``
-    (HDR_GM / HDR_IB).  ``hdrs`` may be None only for HDR_GM with mode NONE; returns ``hdrs``."""
+    (HDR_GM / HDR_IB).  ``hdrs`` may be None only for HDR_GM with mode NONE; returns ``hdrs``.
+
+    HDR_QUADRICS (src/path/quadrics/sendFrag.h:766-880): 128-byte headers, bytes [0, 64) and [68, 124) already
+    filled; a fragment of at most 52 bytes is copied into its header at +72 (its ``dst`` is ignored), a longer one
+    to ``dst`` -- or, with copylen 0, only checksummed -- then dataChecksum @64 and the header checksum @124.
+    ``hdrs`` is required in every mode."""
     _require_cuda(descs, "descs")
     count = descs.numel() * descs.element_size() // 32 if n is None else int(n)
     if count * 32 > descs.numel() * descs.element_size():
@@ -284,7 +296,7 @@ def send_pack_batch(descs: torch.Tensor, hdrs: torch.Tensor | None, hdr_stride: 
             raise ValueError("hdrs is required unless kind is HDR_GM and mode is NONE")
     else:
         _require_cuda(hdrs, "hdrs")
-        if count and offset + (count - 1) * hdr_stride + SEND_HDR_BYTES > hdrs.numel() * hdrs.element_size():
+        if count and offset + (count - 1) * hdr_stride + hdr_bytes(kind) > hdrs.numel() * hdrs.element_size():
             raise ValueError(f"hdrs is too small for {count} headers of stride {hdr_stride}")
         ptr = hdrs.data_ptr() + offset
     check(lib().lampi_send_pack_batch(descs.data_ptr(), count, ptr, hdr_stride, kind, mode | rows_hint_bits(rows_hint),
@@ -299,17 +311,29 @@ def msg_send_pack(msg: torch.Tensor, frag_len: int, ring: torch.Tensor, slot_str
     """A device message made a wire-ready ring: fragment k copied to ``ring`` + k*slot_stride + 72 with its checksum
     fused, and slot k's whole 72-byte header built on the device from ``tmpl`` (72 bytes; dataLength @20,
     frag_seq @32 = frag_seq0 + k*frag_seq_step, sendFragDescPtr @48 = desc_ptr0 + k*desc_ptr_stride,
-    dataSeqOffset @56 = seq_offset0 + k*frag_len, then @64 / @68 of ``kind``).  Returns ``ring``."""
+    dataSeqOffset @56 = seq_offset0 + k*frag_len, then @64 / @68 of ``kind``).  Returns ``ring``.
+
+    HDR_QUADRICS: slot k is a 128-byte envelope -- ``tmpl``'s 72 bytes with the fields above, dataElanAddr @68 =
+    tmpl's + k*frag_len, data[] @72 zero, then @64 / @124 -- with a fragment of at most 52 bytes placed in data[] and
+    a longer one copied to slot + 128 (slot_stride >= 128 + frag_len) or, with slot_stride == 128 (a bare envelope
+    queue), checksummed only."""
     _require_cuda(msg, "msg")
     _require_cuda(ring, "ring")
     nbytes = msg.numel() * msg.element_size() if msg_len is None else int(msg_len)
     if nbytes > msg.numel() * msg.element_size():
         raise ValueError("msg_len exceeds the tensor")
-    if frag_len < 1 or slot_stride < SEND_HDR_BYTES + frag_len:
-        raise ValueError("slot_stride must hold the header and a whole fragment")
-    n = (nbytes + frag_len - 1) // frag_len if nbytes else 1
+    hb = hdr_bytes(kind)
+    n = (nbytes + frag_len - 1) // frag_len if nbytes and frag_len >= 1 else 1
     last = nbytes - (n - 1) * frag_len
-    if (n - 1) * slot_stride + SEND_HDR_BYTES + last > ring.numel() * ring.element_size():
+    if kind == HDR_QUADRICS:
+        if frag_len < 1 or slot_stride < hb or (frag_len > QUADRICS_INLINE_BYTES and slot_stride != hb
+                                                and slot_stride < hb + frag_len):
+            raise ValueError("slot_stride must be 128 (envelopes only) or hold the envelope and a whole fragment")
+        if slot_stride == hb or last <= QUADRICS_INLINE_BYTES:
+            last = 0  # (nothing is written after the last envelope)
+    elif frag_len < 1 or slot_stride < hb + frag_len:
+        raise ValueError("slot_stride must hold the header and a whole fragment")
+    if (n - 1) * slot_stride + hb + last > ring.numel() * ring.element_size():
         raise ValueError("ring is too small")
     t = np.ascontiguousarray(np.frombuffer(bytes(tmpl), dtype=np.uint8) if not isinstance(tmpl, np.ndarray)
                              else tmpl.view(np.uint8).reshape(-1))
@@ -550,18 +574,21 @@ def recv_unpack_batch(descs: torch.Tensor, hdrs: torch.Tensor | None, hdr_stride
     tested as ``kind`` (HDR_GM / HDR_IB) says; a fragment whose header fails is dropped (copied RECV_HDR_BAD, nothing
     read or delivered), the others go through CopyToApp against the header's dataChecksum @64 (copied = bytes
     delivered, or RECV_DATA_BAD).  Returns (copied int64[n], csum int32[n], hdr_mask, data_mask, nbad int32[2] --
-    bad headers, corrupt payloads).  ``hdrs`` may be None with mode NONE (no header is read)."""
+    bad headers, corrupt payloads).  ``hdrs`` may be None with mode NONE (no header is read).
+
+    HDR_QUADRICS (src/path/quadrics/path.cc:839-900): 128-byte headers; a fragment of 1..52 bytes is read from its
+    header at +72 (the descriptor's ``frag`` is ignored), so ``hdrs`` is required in every mode."""
     _require_cuda(descs, "descs")
     count = descs.numel() * descs.element_size() // 32 if n is None else int(n)
     if count * 32 > descs.numel() * descs.element_size():
         raise ValueError("n exceeds the descriptor tensor")
     ptr = None
     if hdrs is None:
-        if (mode & 0xFF) != NONE:
-            raise ValueError("hdrs is required unless mode is NONE (checksumming off)")
+        if (mode & 0xFF) != NONE or kind == HDR_QUADRICS:
+            raise ValueError("hdrs is required unless mode is NONE (checksumming off) and kind is not HDR_QUADRICS")
     else:
         _require_cuda(hdrs, "hdrs")
-        if count and offset + (count - 1) * hdr_stride + SEND_HDR_BYTES > hdrs.numel() * hdrs.element_size():
+        if count and offset + (count - 1) * hdr_stride + hdr_bytes(kind) > hdrs.numel() * hdrs.element_size():
             raise ValueError(f"hdrs is too small for {count} headers of stride {hdr_stride}")
         ptr = hdrs.data_ptr() + offset
     copied, csum, hmask, dmask, nbad = _unpack_out(count, descs.device)
@@ -579,11 +606,14 @@ def msg_recv_unpack(ring: torch.Tensor, nslots: int, slot_stride: int, app: torc
     = the 72-byte header at ``ring`` + k*slot_stride and its payload at +72, in any order; its length is the
     header's dataLength @20 (more than slot_stride - 72: malformed, dropped like a failed header), its destination
     ``app`` + (dataSeqOffset @56 - seq_offset0 mod 2^64), cut at ``app_len`` (default: the whole tensor).  Returns
-    (copied, csum, hdr_mask, data_mask, nbad) as recv_unpack_batch, indexed by slot."""
+    (copied, csum, hdr_mask, data_mask, nbad) as recv_unpack_batch, indexed by slot.
+
+    HDR_QUADRICS: 128-byte envelopes, the payload at slot + 72 when dataLength <= 52, else at slot + 128 (more than
+    slot_stride - 128: malformed)."""
     _require_cuda(ring, "ring")
     _require_cuda(app, "app")
     count = int(nslots)
-    if count < 0 or slot_stride < SEND_HDR_BYTES:
+    if count < 0 or slot_stride < hdr_bytes(kind):
         raise ValueError("slot_stride must hold the header")
     if count * slot_stride > ring.numel() * ring.element_size():
         raise ValueError("ring is too small (every slot may be read whole)")
