@@ -666,6 +666,68 @@ int lampi_chain_copy_to_app_batch(const lampi_copy_desc *d_pieces, size_t npiece
                                   uint32_t *d_csum, uint32_t *d_mask, uint32_t *d_nbad, int mode, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Typemap forms of the one-call send and receive steps: the non-contiguous datatype branch of
+ * gmSendFragDesc::init (ref src/path/gm/sendFrag.cc:157-217, src/path/ib/sendFrag.cc:140-203) and of
+ * RecvDesc_t::CopyToApp (src/path/common/BaseDesc.cc:72-163, 326-340) without per-piece descriptors.  They mirror
+ * lampi_msg_send_pack / lampi_msg_recv_unpack and take the datatype's typemap itself in place of a contiguous
+ * message or application buffer.
+ *
+ * Address rule.  Packed byte p of the message (0 <= p < count * packed_size) lives at
+ *   d_base + (p / packed_size) * extent + pairs[i].offset + (r - pairs[i].seq_offset),
+ * r = p % packed_size, i the last pair with seq_offset <= r.  Pairs are in packed order: seq_offset[0] = 0,
+ * seq_offset[i+1] = seq_offset[i] + size[i], size >= 1, the sizes sum to packed_size.  An inconsistent
+ * device-resident typemap is the caller's error, as a bad address in a descriptor is.  Offsets may be negative.
+ * ---------------------------------------------------------------------------------- */
+
+/* One typemap pair exactly as the reference holds it (ULMTypeMapElt_t, src/include/ulm/types.h:92-96): 24 bytes,
+ * so dtype->type_map uploads as it is. */
+typedef struct lampi_tmap_elt { uint64_t size; int64_t offset; int64_t seq_offset; } lampi_tmap_elt;
+
+typedef struct lampi_tmap {          /* HOST memory, read during the call; 40 bytes */
+    const lampi_tmap_elt *d_pairs;   /* DEVICE memory, num_pairs entries, uploaded once per committed datatype */
+    uint64_t extent;                 /* dtype->extent */
+    uint64_t packed_size;            /* dtype->packed_size == the sum of the sizes */
+    uint64_t count;                  /* elements in the message: tot_cnt = length / packed_size */
+    uint32_t num_pairs, reserved;    /* reserved = 0 */
+} lampi_tmap;
+
+/* Send.  Fragment j is packed bytes [pack_off + j*frag_len, min(.. + frag_len, pack_off + pack_len)) -- pack_off
+ * is the send window of gm/path.cc:104-118 and may fall in the middle of a pair --, gathered to
+ * d_ring + j*slot_stride + 72 with the uicrc from CRC_INITIAL_REGISTER / the uicsum from a fresh state of those
+ * packed bytes (the value the reference chains over the pieces), and all 72 header bytes of slot j are written as
+ * lampi_msg_send_pack writes them: h_fill's series indexed by j, dataLength = the fragment's packed length,
+ * dataSeqOffset = seq_offset0 + j*frag_len, @64 / @68 by the GM / IB table above (LAMPI_CSUM_NONE and IB's zero
+ * for an empty fragment included).  pack_len == 0: one empty fragment, its header written.  d_ring and
+ * slot_stride 8-byte aligned, slot_stride >= 72 + frag_len, 1 <= frag_len <= 2^32 - 1; d_base any alignment.
+ * hipErrorInvalidValue, nothing written: NULL h_tmap or d_pairs, num_pairs == 0, packed_size == 0, a nonzero
+ * reserved, count * packed_size >= 2^63, pack_off + pack_len > count * packed_size, more than 2^32 - 1 fragments,
+ * any bit in mode beyond the three modes (no hint, no LAMPI_CSUM_BY_BYTES), hdr_kind other than GM or IB.
+ * LAMPI_SEND_HDR_QUADRICS is refused: its inline payloads are placed by a pass that reads a contiguous message;
+ * gathered inline payloads are not built yet.
+ * One 4 KiB row of the packed bytes per wave, each byte loaded once from its piece and stored once; scratch is a
+ * word per row from the stream's pooled buffers (the call may be captured into a graph). */
+int lampi_tmap_send_pack(const void *d_base, const lampi_tmap *h_tmap, uint64_t pack_off, uint64_t pack_len,
+                         size_t frag_len, void *d_ring, size_t slot_stride, const lampi_send_hdr_fill *h_fill,
+                         int hdr_kind, int mode, void *stream);
+
+/* Receive.  Exactly lampi_msg_recv_unpack's rules with app_len = count * packed_size and the delivery mapped
+ * through the address rule: Offset = (dataSeqOffset - seq_offset0) mod 2^64; a dataLength > slot_stride - 72 is
+ * malformed and dropped as LAMPI_RECV_HDR_BAD in every mode; Offset >= app_len: nothing copied or checksummed,
+ * DataOK; otherwise the first min(dataLength, app_len - Offset) packed bytes are scattered to their pieces, all
+ * dataLength bytes are checksummed and compared with the word @64 (LAMPI_RECV_DATA_BAD, the masks, the counts and
+ * d_csum as in the ring form); a fragment whose header fails is dropped -- no payload byte read, no application
+ * byte written.  Bytes between the pieces are never written.
+ * One departure from the reference: its non_contiguous_copy tests AppBufferLen only for <= 0 and then walks the
+ * sender's msgLength (BaseDesc.cc:72-163), so a truncated receive writes past the posted buffer and fails
+ * CheckData.  This library never writes past `count` elements: truncation is treated as the contiguous
+ * CopyFunction treats it (lengthToCopy = min(length, AppBufferLen), checksum over the whole payload).
+ * Refusals as the send form's (nslots < 2^32; d_nbad required); LAMPI_SEND_HDR_QUADRICS is refused. */
+int lampi_tmap_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride, int hdr_kind,
+                           void *d_base, const lampi_tmap *h_tmap, uint64_t seq_offset0,
+                           int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask, uint32_t *d_data_mask,
+                           uint32_t *d_nbad /* 2 words */, int mode, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Utilities (bench/test support, device-side).
  * ---------------------------------------------------------------------------------- */
 

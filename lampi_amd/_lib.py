@@ -92,6 +92,25 @@ class SendHdrFill(ctypes.Structure):
 
 assert ctypes.sizeof(SendHdrFill) == 112
 
+
+class TmapElt(ctypes.Structure):
+    """struct lampi_tmap_elt (24 bytes): size u64, offset i64, seq_offset i64 -- ULMTypeMapElt_t as it is."""
+
+    _fields_ = [("size", ctypes.c_uint64), ("offset", ctypes.c_int64), ("seq_offset", ctypes.c_int64)]
+
+
+assert ctypes.sizeof(TmapElt) == 24
+
+
+class Tmap(ctypes.Structure):
+    """struct lampi_tmap (40 bytes, host): d_pairs (device), extent, packed_size, count u64, num_pairs, reserved u32."""
+
+    _fields_ = [("d_pairs", ctypes.c_void_p), ("extent", ctypes.c_uint64), ("packed_size", ctypes.c_uint64),
+                ("count", ctypes.c_uint64), ("num_pairs", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(Tmap) == 40
+
 _lock = threading.Lock()
 _lib = None
 
@@ -136,6 +155,11 @@ PROTOTYPES = {
     "lampi_msg_recv_unpack": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, ctypes.c_int, c_void_p, c_size_t,
                                              ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              ctypes.c_int, c_void_p]),
+    "lampi_tmap_send_pack": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_size_t, c_void_p,
+                                            c_size_t, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p]),
+    "lampi_tmap_recv_unpack": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, ctypes.c_int, c_void_p, c_void_p,
+                                              ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              ctypes.c_int, c_void_p]),
     "lampi_chain_csum_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
                                                       ctypes.c_int, c_void_p]),
     "lampi_header_csum_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, ctypes.c_uint32, ctypes.c_uint32,

@@ -7176,6 +7176,9 @@ hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag
     return scratch_done(s, vals, pooled, e);
 }
 
+// ---- the typemap forms of both steps (lampi_tmap_send_pack / lampi_tmap_recv_unpack) -----------------------
+#include "tmap_kernels.h"
+
 hipError_t launch_chain(const lampi_copy_desc *d, size_t npieces, const uint32_t *first, size_t nfrags, uint32_t *out,
                         int mode, const uint32_t *img, uint32_t *vals, uint32_t *phase, hipStream_t s,
                         const ChainVerdict *verdict) {

@@ -91,6 +91,17 @@ hipError_t launch_recv_unpack(const lampi_recv_desc *d, size_t n, const uint8_t 
 hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slot_stride, int kind, uint8_t *app,
                                   size_t app_len, uint64_t seq0, int64_t *copied, uint32_t *csum, uint32_t *hmask,
                                   uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s);
+// Both steps through a datatype's typemap (tmap_kernels.h): one 4 KiB row of a fragment's packed bytes per wave,
+// gathered from / scattered to the typemap's pieces of base, checksummed from the registers that hold it; the
+// headers built and stamped (send) or tested first and the verdicts given last (receive) as the ring forms do.
+// kind: GM or IB; n = the fragments of [pack_off, pack_off + pack_len), one for an empty window.
+hipError_t launch_tmap_send_pack(const uint8_t *base, const lampi_tmap &tm, uint64_t pack_off, uint64_t pack_len,
+                                 size_t frag_len, uint8_t *ring, size_t slot_stride, const lampi_send_hdr_fill &fill,
+                                 size_t n, int kind, int mode, const uint32_t *img, hipStream_t s);
+hipError_t launch_tmap_recv_unpack(const uint8_t *ring, size_t nslots, size_t slot_stride, int kind, uint8_t *base,
+                                   const lampi_tmap &tm, uint64_t seq0, int64_t *copied, uint32_t *csum,
+                                   uint32_t *hmask, uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img,
+                                   hipStream_t s);
 // headerChecksum per header / receiver header check / CheckData (mask bit set = corrupt).
 hipError_t launch_header_csum(const uint8_t *hdrs, size_t n, size_t stride, uint32_t crclen, uint32_t word_count,
                               int mode, const uint32_t *img, uint8_t *out, size_t out_stride, hipStream_t s);

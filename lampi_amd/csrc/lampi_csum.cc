@@ -849,6 +849,63 @@ int lampi_msg_send_pack(const void *d_msg, size_t msg_len, size_t frag_len, void
                                        n, hdr_kind, mode, img, (hipStream_t)stream, crc_grid(dev)));
 }
 
+// What both typemap forms refuse: the mode's extra bits, Quadrics (its inline payloads are placed from a contiguous
+// message), a typemap that cannot be walked.  *total = count * packed_size (< 2^63).
+static bool tmap_args_ok(const lampi_tmap *h_tmap, int hdr_kind, int mode, uint64_t *total) {
+    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE) return false;
+    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return false;
+    if (!h_tmap || !h_tmap->d_pairs || h_tmap->num_pairs == 0 || h_tmap->packed_size == 0 || h_tmap->reserved != 0)
+        return false;
+    if (h_tmap->count > (((uint64_t)1 << 63) - 1) / h_tmap->packed_size) return false;
+    *total = h_tmap->count * h_tmap->packed_size;
+    return true;
+}
+
+// The send step through a typemap (ref src/path/gm/sendFrag.cc:157-217, src/path/ib/sendFrag.cc:140-203): no
+// descriptors, no per-piece values (tmap_kernels.h: tmap_row_kernel, launch_tmap_send_pack).
+int lampi_tmap_send_pack(const void *d_base, const lampi_tmap *h_tmap, uint64_t pack_off, uint64_t pack_len,
+                         size_t frag_len, void *d_ring, size_t slot_stride, const lampi_send_hdr_fill *h_fill,
+                         int hdr_kind, int mode, void *stream) {
+    uint64_t total = 0;
+    if (!tmap_args_ok(h_tmap, hdr_kind, mode, &total)) return to_int(hipErrorInvalidValue);
+    if (pack_off > total || pack_len > total - pack_off) return to_int(hipErrorInvalidValue);
+    if (frag_len == 0 || frag_len > 0xFFFFFFFFull || !d_ring || !h_fill || ((uintptr_t)d_ring & 7u) ||
+        (slot_stride & 7u) || slot_stride < 72 || slot_stride - 72 < frag_len || (pack_len && !d_base))
+        return to_int(hipErrorInvalidValue);
+    const uint64_t n = pack_len ? (pack_len - 1) / frag_len + 1 : 1;  // (an empty window: one empty fragment)
+    if (n > 0xFFFFFFFFull) return to_int(hipErrorInvalidValue);
+    int dev = 0;
+    hipError_t e = current_device(&dev);
+    if (e != hipSuccess) return to_int(e);
+    const uint32_t *img = nullptr;
+    e = device_tables(dev, &img);
+    if (e != hipSuccess) return to_int(e);
+    return to_int(launch_tmap_send_pack((const uint8_t *)d_base, *h_tmap, pack_off, pack_len, frag_len, (uint8_t *)d_ring,
+                                        slot_stride, *h_fill, (size_t)n, hdr_kind, mode, img, (hipStream_t)stream));
+}
+
+// The receive step through a typemap (ref src/path/common/BaseDesc.cc:72-163, 326-340): lampi_msg_recv_unpack's
+// rules, the delivery scattered to the typemap's pieces (tmap_kernels.h: launch_tmap_recv_unpack).
+int lampi_tmap_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride, int hdr_kind, void *d_base,
+                           const lampi_tmap *h_tmap, uint64_t seq_offset0, int64_t *d_copied, uint32_t *d_csum,
+                           uint32_t *d_hdr_mask, uint32_t *d_data_mask, uint32_t *d_nbad, int mode, void *stream) {
+    uint64_t total = 0;
+    if (!tmap_args_ok(h_tmap, hdr_kind, mode, &total)) return to_int(hipErrorInvalidValue);
+    if (((uintptr_t)d_ring & 7u) || (slot_stride & 7u) || slot_stride < 72) return to_int(hipErrorInvalidValue);
+    if (!d_nbad || nslots > 0xFFFFFFFFull || (total && !d_base) ||
+        (nslots && (!d_ring || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask)))
+        return to_int(hipErrorInvalidValue);
+    int dev = 0;
+    hipError_t e = current_device(&dev);
+    if (e != hipSuccess) return to_int(e);
+    const uint32_t *img = nullptr;
+    e = device_tables(dev, &img);
+    if (e != hipSuccess) return to_int(e);
+    return to_int(launch_tmap_recv_unpack((const uint8_t *)d_ring, nslots, slot_stride, hdr_kind, (uint8_t *)d_base,
+                                          *h_tmap, seq_offset0, d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode,
+                                          img, (hipStream_t)stream));
+}
+
 int lampi_chain_csum_batch_strided(const lampi_copy_desc *d_pieces, size_t npieces, const uint32_t *d_first,
                                    size_t nfrags, void *d_out, size_t out_stride, int mode, void *stream) {
     if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)

@@ -10,9 +10,10 @@ import numpy as np
 import torch
 
 from ._lib import (BY_BYTES, CRC32, CRC_INITIAL_REGISTER, HDR_GM, HDR_IB, HDR_QUADRICS, NONE, RECV_DATA_BAD, RECV_HDR_BAD,
-                   SUM32, SendHdrFill, check, lib, rows_hint_bits)
+                   SUM32, SendHdrFill, Tmap, check, lib, rows_hint_bits)
 
 __all__ = ["CRC32", "SUM32", "NONE", "HDR_GM", "HDR_IB", "HDR_QUADRICS", "RECV_DATA_BAD", "RECV_HDR_BAD", "recv_unpack_batch", "msg_recv_unpack",
+           "make_tmap", "tmap_send_pack", "tmap_recv_unpack",
            "send_pack_batch", "msg_send_pack","chain_copy_to_app_batch", "frag_bcopy_batch_strided", "msg_bcopy_strided",
            "chain_csum_batch_strided", "header_csum_batch_strided", "frag_csum_batch", "diag_frag_csum_batch_per_wave", "frag_csum64_batch", "frag_bcopy_batch", "msg_bcopy", "msg_csum", "fill_stream", "fill_stream_frags",
            "make_descs", "make_copy_descs", "as_u32", "chain_csum_batch", "header_csum_batch", "header_check_batch", "check_data_batch",
@@ -352,6 +353,94 @@ def msg_send_pack(msg: torch.Tensor, frag_len: int, ring: torch.Tensor, slot_str
     return ring
 
 
+class DeviceTmap:
+    """A committed datatype's typemap on the device (make_tmap): ``struct`` is the host ``lampi_tmap`` the C ABI
+    reads during a call, ``pairs`` the device tensor its d_pairs points into -- kept alive here beside it."""
+
+    def __init__(self, struct: Tmap, pairs: torch.Tensor, lo: int, hi: int):
+        self.struct, self.pairs = struct, pairs
+        self.lo, self.hi = lo, hi  # the lowest piece offset and the highest piece end within an element
+
+    extent = property(lambda self: int(self.struct.extent))
+    packed_size = property(lambda self: int(self.struct.packed_size))
+    count = property(lambda self: int(self.struct.count))
+    num_pairs = property(lambda self: int(self.struct.num_pairs))
+
+    def span(self) -> tuple[int, int]:
+        """[lo, hi) byte range, relative to the base address, that the message's pieces lie in."""
+        if self.count == 0:
+            return 0, 0
+        steps = (0, (self.count - 1) * self.extent)
+        return self.lo + min(steps), self.hi + max(steps)
+
+
+def make_tmap(pairs, extent: int, count: int, device) -> DeviceTmap:
+    """Upload a typemap: ``pairs`` is [num_pairs, 2] (size, offset) in packed order -- seq_offset is the running sum
+    of the sizes -- or [num_pairs, 3] with seq_offset given (ULMTypeMapElt_t as it is); ``extent`` the datatype's
+    extent, ``count`` the elements in the message."""
+    a = np.asarray(pairs, dtype=np.int64)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] not in (2, 3):
+        raise ValueError("pairs must be [num_pairs >= 1, 2 or 3]")
+    if np.any(a[:, 0] < 1):
+        raise ValueError("every pair's size must be at least 1")
+    seq = np.concatenate(([0], np.cumsum(a[:-1, 0])))
+    if a.shape[1] == 3 and not np.array_equal(a[:, 2], seq):
+        raise ValueError("seq_offset must be the running sum of the sizes")
+    host = np.empty((a.shape[0], 3), dtype=np.int64)
+    host[:, 0], host[:, 1], host[:, 2] = a[:, 0], a[:, 1], seq
+    t = torch.from_numpy(host).to(device)
+    st = Tmap()
+    st.d_pairs = t.data_ptr()
+    st.extent, st.packed_size, st.count = int(extent), int(a[:, 0].sum()), int(count)
+    st.num_pairs, st.reserved = a.shape[0], 0
+    return DeviceTmap(st, t, int(a[:, 1].min()), int((a[:, 1] + a[:, 0]).max()))
+
+
+def _tmap_base(base: torch.Tensor, base_offset: int, tmap: DeviceTmap) -> int:
+    """The device address of the typemap's origin: byte ``base_offset`` of ``base``; every piece must lie inside."""
+    _require_cuda(base, "base")
+    lo, hi = tmap.span()
+    if base_offset + lo < 0 or base_offset + hi > base.numel() * base.element_size():
+        raise ValueError("the typemap's pieces reach outside the base tensor")
+    return base.data_ptr() + base_offset
+
+
+def tmap_send_pack(base: torch.Tensor, tmap: DeviceTmap, frag_len: int, ring: torch.Tensor, slot_stride: int, tmpl,
+                   frag_seq0: int = 0, frag_seq_step: int = 0, desc_ptr0: int = 0, desc_ptr_stride: int = 0,
+                   seq_offset0: int = 0, kind: int = HDR_GM, mode: int = CRC32, pack_off: int = 0,
+                   pack_len: int | None = None, base_offset: int = 0,
+                   stream: torch.cuda.Stream | None = None) -> torch.Tensor:
+    """msg_send_pack through a datatype's typemap (src/path/gm/sendFrag.cc:157-217): fragment j = packed bytes
+    [pack_off + j*frag_len, ...) of the ``tmap.count`` elements whose origin is byte ``base_offset`` of ``base``
+    (default window: everything from pack_off on), gathered to ``ring`` + j*slot_stride + 72 with the checksum of
+    the packed bytes, the 72-byte headers built as msg_send_pack builds them.  HDR_GM / HDR_IB.  Returns ``ring``."""
+    _require_cuda(ring, "ring")
+    total = tmap.count * tmap.packed_size
+    plen = max(total - pack_off, 0) if pack_len is None else int(pack_len)
+    if frag_len < 1 or slot_stride < SEND_HDR_BYTES + frag_len:
+        raise ValueError("slot_stride must hold the header and a whole fragment")
+    n = (plen + frag_len - 1) // frag_len if plen else 1
+    last = plen - (n - 1) * frag_len
+    if (n - 1) * slot_stride + SEND_HDR_BYTES + last > ring.numel() * ring.element_size():
+        raise ValueError("ring is too small")
+    t = np.ascontiguousarray(np.frombuffer(bytes(tmpl), dtype=np.uint8) if not isinstance(tmpl, np.ndarray)
+                             else tmpl.view(np.uint8).reshape(-1))
+    if t.size != SEND_HDR_BYTES:
+        raise ValueError("tmpl must be 72 bytes")
+    fill = SendHdrFill()
+    fill.tmpl[:] = t.tolist()
+    m64 = 2**64 - 1
+    fill.frag_seq0, fill.frag_seq_step = frag_seq0 & m64, frag_seq_step & m64
+    fill.desc_ptr0, fill.desc_ptr_stride = desc_ptr0 & m64, desc_ptr_stride & m64
+    fill.seq_offset0 = seq_offset0 & m64
+    import ctypes
+
+    check(lib().lampi_tmap_send_pack(_tmap_base(base, base_offset, tmap), ctypes.addressof(tmap.struct), pack_off, plen,
+                                     frag_len, ring.data_ptr(), slot_stride, ctypes.addressof(fill), kind, mode,
+                                     _stream_handle(stream)), "lampi_tmap_send_pack")
+    return ring
+
+
 def chain_csum_batch(pieces: torch.Tensor, first, mode: int = CRC32, out: torch.Tensor | None = None,
                      stream: torch.cuda.Stream | None = None) -> torch.Tensor:
     """Chained checksum per fragment over its typemap pieces (``lampi_copy_desc`` rows of
@@ -626,6 +715,29 @@ def msg_recv_unpack(ring: torch.Tensor, nslots: int, slot_stride: int, app: torc
                                       seq_offset0 & (2**64 - 1), copied.data_ptr(), csum.data_ptr(), hmask.data_ptr(),
                                       dmask.data_ptr(), nbad.data_ptr(), mode, _stream_handle(stream)),
           "lampi_msg_recv_unpack")
+    return copied[:count], csum[:count], hmask, dmask, nbad
+
+
+def tmap_recv_unpack(ring: torch.Tensor, nslots: int, slot_stride: int, base: torch.Tensor, tmap: DeviceTmap,
+                     kind: int = HDR_GM, mode: int = CRC32, seq_offset0: int = 0, base_offset: int = 0,
+                     stream: torch.cuda.Stream | None = None):
+    """msg_recv_unpack through a datatype's typemap (src/path/common/BaseDesc.cc:72-163, 326-340): the same rules
+    with app_len = tmap.count * tmap.packed_size, the delivered packed bytes scattered to the typemap's pieces of
+    the elements whose origin is byte ``base_offset`` of ``base``; nothing is written between the pieces or past
+    ``tmap.count`` elements.  HDR_GM / HDR_IB.  Returns (copied, csum, hdr_mask, data_mask, nbad), indexed by slot."""
+    import ctypes
+
+    _require_cuda(ring, "ring")
+    count = int(nslots)
+    if count < 0 or slot_stride < SEND_HDR_BYTES:
+        raise ValueError("slot_stride must hold the header")
+    if count * slot_stride > ring.numel() * ring.element_size():
+        raise ValueError("ring is too small (every slot may be read whole)")
+    copied, csum, hmask, dmask, nbad = _unpack_out(count, ring.device)
+    check(lib().lampi_tmap_recv_unpack(ring.data_ptr(), count, slot_stride, kind, _tmap_base(base, base_offset, tmap),
+                                       ctypes.addressof(tmap.struct), seq_offset0 & (2**64 - 1), copied.data_ptr(),
+                                       csum.data_ptr(), hmask.data_ptr(), dmask.data_ptr(), nbad.data_ptr(), mode,
+                                       _stream_handle(stream)), "lampi_tmap_recv_unpack")
     return copied[:count], csum[:count], hmask, dmask, nbad
 
 
