@@ -272,3 +272,34 @@ def expect_ring(oracle, hring, nslots, stride, app, app_len, seq0, kind, mode):
     aoffs = np.array([o if r > 0 else 0 for o, r in zip(off, room)], np.uint64)
     poffs = np.arange(nslots, dtype=np.uint64) * np.uint64(stride) + np.uint64(HDR)
     return expect(oracle, hring, poffs, np.where(well, lens, 0), H, well, app, aoffs, room, kind, mode)
+
+
+def pack_slots_at(oracle, rng, hring, m, offs, lens, stride, seq0, kind, mode, order=None):
+    """pack_slots with a packed offset and a length of its own per fragment: fragment k -- m[offs[k] : offs[k] +
+    lens[k]] -- in slot order[k], dataLength @20 = lens[k], dataSeqOffset @56 = seq0 + offs[k] (mod 2^64).  No two
+    fragments' packed ranges may overlap (a call's result must not depend on the order its rows run in).  Returns
+    (n, the slot of each fragment)."""
+    offs, lens = np.asarray(offs, np.int64), np.asarray(lens, np.int64)
+    n = len(lens)
+    assert n >= 1 and len(offs) == n and int(lens.min()) >= 0 and int(lens.max()) <= stride - HDR
+    assert int((offs + lens).max()) <= len(m)
+    by = np.argsort(offs, kind="stable")
+    full = by[lens[by] > 0]
+    assert np.all((offs + lens)[full][:-1] <= offs[full][1:]), "packed ranges overlap"
+    order = np.arange(n) if order is None else np.asarray(order)
+    assert sorted(int(x) for x in order) == list(range(n))
+    h = rng.integers(0, 256, size=(n, HDR), dtype=np.uint8)
+    h[:, LEN_AT:LEN_AT + 4] = lens.astype("<u4").view(np.uint8).reshape(n, 4)
+    h[:, SEQOFF_AT:SEQOFF_AT + 8] = np.array([(seq0 + int(o)) & M64 for o in offs], "<u8").view(np.uint8).reshape(n, 8)
+    if mode != NONE:
+        vals = oracle.desc_batch(m if len(m) else np.zeros(1, np.uint8), np.where(lens > 0, offs, 0).astype(np.uint64),
+                                 lens.astype(np.uint32), np.full(n, 0xFFFFFFFF, np.uint32) if mode == CRC else None,
+                                 mode)
+        w = _stamp_all(oracle, h[:, :DCSUM], vals, lens == 0, kind, mode)
+        h[:, DCSUM:HCSUM] = w[0].astype("<u4").view(np.uint8).reshape(n, 4)
+        h[:, HCSUM:] = w[1].astype("<u4").view(np.uint8).reshape(n, 4)
+    for k in range(n):
+        s, c = int(order[k]) * stride, int(lens[k])
+        hring[s:s + HDR] = h[k]
+        hring[s + HDR:s + HDR + c] = m[int(offs[k]):int(offs[k]) + c]
+    return n, order
