@@ -727,6 +727,79 @@ int lampi_tmap_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride
                            int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask, uint32_t *d_data_mask,
                            uint32_t *d_nbad /* 2 words */, int mode, void *stream);
 
+/* Descriptor forms of the typemap steps: one call for the fragments of several messages, as gmPath::receive /
+ * ibPath::receive drain them (fragments of whatever receives are posted, their slots interleaved) and as the send
+ * loop packs what the clear-to-send windows allow.  They are to the typemap forms above what
+ * lampi_send_pack_batch / lampi_recv_unpack_batch are to the ring forms: every fragment has a record of its own
+ * that names its payload, its window of packed bytes and its message; every message an entry with its typemap and
+ * where its element 0 lives.  Both tables are in DEVICE memory, little-endian. */
+
+/* One message: a committed datatype, its element count and where element 0 lives.  64 bytes. */
+typedef struct lampi_tmap_msg {
+    const lampi_tmap_elt *d_pairs;   /* @0  device, num_pairs entries (ULMTypeMapElt_t as it is) */
+    uint64_t extent;                 /* @8  */
+    uint64_t packed_size;            /* @16 */
+    uint64_t count;                  /* @24 elements in the message; app_len = count * packed_size */
+    uint32_t num_pairs, reserved;    /* @32, @36; reserved = 0 */
+    uint64_t base;                   /* @40 device address of the datatype's origin (any alignment) */
+    uint64_t reserved2[2];           /* @48; 0 */
+} lampi_tmap_msg;
+
+/* One fragment.  32 bytes. */
+typedef struct lampi_tmap_frag {
+    uint64_t payload;   /* @0  device address of the fragment's packed bytes: written by send, read by receive */
+    uint64_t pack_off;  /* @8  first packed byte of the fragment in its message (receive: dataSeqOffset - seq_offset0,
+                               done by the caller) */
+    uint32_t length;    /* @16 packed bytes (receive: length_m; all of them are checksummed) */
+    uint32_t msg;       /* @20 index into the message table */
+    uint64_t reserved;  /* @24 0 */
+} lampi_tmap_frag;
+
+/* The address rule is the one above, applied with the fragment's own message entry (base, extent, packed_size,
+ * pairs).  max_len is the caller's upper bound on any record's length: it fixes the frame at
+ * R = max(1, ceil(max_len / 4096)) rows for the whole launch (as slot_stride - 72 does in lampi_tmap_recv_unpack),
+ * so a batch whose lengths differ widely pays for padding rows -- batch by size class.
+ *
+ * Send, the mirror of lampi_send_pack_batch: header i is the 72 bytes at (char *)d_hdrs + i*hdr_stride, bytes
+ * [0, 64) filled by the caller; packed bytes [pack_off, pack_off + length) of fragment i's message are gathered to
+ * its payload, and their uicrc from CRC_INITIAL_REGISTER / uicsum from a fresh state is stamped @64 with the
+ * header checksum @68 by the GM / IB table above (LAMPI_CSUM_NONE and IB's zero for an empty fragment included).
+ * Apart from the payloads exactly those words are written.
+ *
+ * Receive, the mirror of lampi_recv_unpack_batch: header i is tested as hdr_kind says; a fragment whose header
+ * fails is dropped as LAMPI_RECV_HDR_BAD (no payload byte read, no application byte written); otherwise CopyToApp
+ * through the typemap: room = app_len - pack_off (0 when pack_off >= app_len), ncopy = min(length, room); room 0:
+ * nothing copied or checksummed, DataOK; else ncopy packed bytes are scattered to their pieces, all `length`
+ * bytes are checksummed and compared with the word @64.  The length comes from the record.  Truncation as in
+ * lampi_tmap_recv_unpack: nothing is written past `count` elements, nothing between the pieces.  d_copied, d_csum,
+ * both masks and both counts exactly as lampi_recv_unpack_batch gives them.  Where two fragments' deliveries
+ * overlap those bytes are unspecified.
+ *
+ * hipErrorInvalidValue, nothing written: d_frags or d_msgs NULL with n > 0; nmsgs == 0 or >= 2^32; n >= 2^32;
+ * hdr_kind other than GM or IB (LAMPI_SEND_HDR_QUADRICS is refused); any bit in mode beyond the three modes;
+ * hdr_stride < 72, d_hdrs or hdr_stride not 4-byte aligned; d_hdrs NULL, unless send with GM and LAMPI_CSUM_NONE
+ * (no header word is written) or receive with LAMPI_CSUM_NONE (no header is read); on receive any NULL output.
+ * n == 0 returns 0; the receive form zeroes both counts.
+ *
+ * Invalid records.  The tables are in device memory, so these are tested on the device, before any division or
+ * address is formed from the record: msg >= nmsgs; length > max_len; an entry with d_pairs NULL, num_pairs == 0 or
+ * packed_size == 0; on send, pack_off + length > count * packed_size.  Send skips such a record: no byte is
+ * copied, its header stays as it is.  Receive drops it as LAMPI_RECV_HDR_BAD in every mode, LAMPI_CSUM_NONE
+ * included (its bit in d_hdr_mask, counted in d_nbad[0], d_csum 0).  An inconsistent but well-formed typemap or
+ * address stays the caller's error.
+ *
+ * No allocation in the stream: a word per row, a word per fragment and the receive records come from the
+ * stream's pooled buffers (inside a capture, from buffers the call owns); both calls may be captured into one
+ * graph on one stream. */
+int lampi_tmap_send_pack_batch(const lampi_tmap_frag *d_frags, size_t n, const lampi_tmap_msg *d_msgs, size_t nmsgs,
+                               uint32_t max_len, void *d_hdrs, size_t hdr_stride, int hdr_kind, int mode,
+                               void *stream);
+
+int lampi_tmap_recv_unpack_batch(const lampi_tmap_frag *d_frags, size_t n, const lampi_tmap_msg *d_msgs, size_t nmsgs,
+                                 uint32_t max_len, const void *d_hdrs, size_t hdr_stride, int hdr_kind,
+                                 int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask, uint32_t *d_data_mask,
+                                 uint32_t *d_nbad /* 2 words */, int mode, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * Utilities (bench/test support, device-side).
  * ---------------------------------------------------------------------------------- */

@@ -19,7 +19,8 @@ __version__ = "0.1.0"
 
 # The receive step in one call lives in :mod:`lampi_amd.device`; the names resolve on first use, so importing the
 # package still needs no torch.
-_DEVICE_EXPORTS = ("recv_unpack_batch", "msg_recv_unpack", "tmap_send_pack", "tmap_recv_unpack")
+_DEVICE_EXPORTS = ("recv_unpack_batch", "msg_recv_unpack", "tmap_send_pack", "tmap_recv_unpack", "make_tmap_msgs",
+                   "make_tmap_frags", "tmap_send_pack_batch", "tmap_recv_unpack_batch")
 
 
 def __getattr__(name):

@@ -111,6 +111,28 @@ class Tmap(ctypes.Structure):
 
 assert ctypes.sizeof(Tmap) == 40
 
+
+class TmapMsg(ctypes.Structure):
+    """struct lampi_tmap_msg (64 bytes, device): one message of the descriptor forms -- its typemap as in Tmap, then
+    base u64 (the device address of the datatype's origin) and two reserved words."""
+
+    _fields_ = [("d_pairs", ctypes.c_void_p), ("extent", ctypes.c_uint64), ("packed_size", ctypes.c_uint64),
+                ("count", ctypes.c_uint64), ("num_pairs", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("base", ctypes.c_uint64), ("reserved2", ctypes.c_uint64 * 2)]
+
+
+assert ctypes.sizeof(TmapMsg) == 64
+
+
+class TmapFrag(ctypes.Structure):
+    """struct lampi_tmap_frag (32 bytes, device): payload u64, pack_off u64, length u32, msg u32, reserved u64."""
+
+    _fields_ = [("payload", ctypes.c_uint64), ("pack_off", ctypes.c_uint64), ("length", ctypes.c_uint32),
+                ("msg", ctypes.c_uint32), ("reserved", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(TmapFrag) == 32
+
 _lock = threading.Lock()
 _lib = None
 
@@ -160,6 +182,11 @@ PROTOTYPES = {
     "lampi_tmap_recv_unpack": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, ctypes.c_int, c_void_p, c_void_p,
                                               ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               ctypes.c_int, c_void_p]),
+    "lampi_tmap_send_pack_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_uint32, c_void_p,
+                                                  c_size_t, ctypes.c_int, ctypes.c_int, c_void_p]),
+    "lampi_tmap_recv_unpack_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_uint32, c_void_p,
+                                                    c_size_t, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, ctypes.c_int, c_void_p]),
     "lampi_chain_csum_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
                                                       ctypes.c_int, c_void_p]),
     "lampi_header_csum_batch_strided": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, ctypes.c_uint32, ctypes.c_uint32,

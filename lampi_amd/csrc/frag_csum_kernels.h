@@ -102,6 +102,17 @@ hipError_t launch_tmap_recv_unpack(const uint8_t *ring, size_t nslots, size_t sl
                                    const lampi_tmap &tm, uint64_t seq0, int64_t *copied, uint32_t *csum,
                                    uint32_t *hmask, uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img,
                                    hipStream_t s);
+// ... over fragment records and a message table (both device memory): every fragment its own payload, window and
+// message; a frame of max(1, ceil(max_len / 4096)) rows for all of them; invalid records are skipped (send) or
+// dropped (receive) on the device.  hdrs: the caller's headers (send: null with GM and checksumming off; receive:
+// not read with checksumming off).
+hipError_t launch_tmap_send_pack_batch(const lampi_tmap_frag *frags, size_t n, const lampi_tmap_msg *msgs, size_t nmsgs,
+                                       uint32_t max_len, uint8_t *hdrs, size_t hdr_stride, int kind, int mode,
+                                       const uint32_t *img, hipStream_t s);
+hipError_t launch_tmap_recv_unpack_batch(const lampi_tmap_frag *frags, size_t n, const lampi_tmap_msg *msgs,
+                                         size_t nmsgs, uint32_t max_len, const uint8_t *hdrs, size_t hdr_stride,
+                                         int kind, int64_t *copied, uint32_t *csum, uint32_t *hmask, uint32_t *dmask,
+                                         uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s);
 // headerChecksum per header / receiver header check / CheckData (mask bit set = corrupt).
 hipError_t launch_header_csum(const uint8_t *hdrs, size_t n, size_t stride, uint32_t crclen, uint32_t word_count,
                               int mode, const uint32_t *img, uint8_t *out, size_t out_stride, hipStream_t s);

@@ -906,6 +906,59 @@ int lampi_tmap_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride
                                           img, (hipStream_t)stream));
 }
 
+// What both descriptor forms of the typemap steps refuse on the host (the records and the message table are device
+// memory: what they hold is tested there, tmap_kernels.h: tmap_record).
+static bool tmap_batch_args_ok(size_t n, size_t nmsgs, uint32_t max_len, const void *d_hdrs, size_t hdr_stride,
+                               int hdr_kind, int mode) {
+    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE) return false;
+    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return false;
+    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < 72) return false;
+    if (nmsgs == 0 || nmsgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return false;
+    const size_t R = std::max<size_t>(1, ((size_t)max_len + 4095) / 4096);  // the frame's rows: a word of scratch each
+    return n <= SIZE_MAX / sizeof(uint32_t) / R;
+}
+
+// The typemap send step over fragment records (tmap_kernels.h: launch_tmap_send_pack_batch)
+int lampi_tmap_send_pack_batch(const lampi_tmap_frag *d_frags, size_t n, const lampi_tmap_msg *d_msgs, size_t nmsgs,
+                               uint32_t max_len, void *d_hdrs, size_t hdr_stride, int hdr_kind, int mode,
+                               void *stream) {
+    if (!tmap_batch_args_ok(n, nmsgs, max_len, d_hdrs, hdr_stride, hdr_kind, mode)) return to_int(hipErrorInvalidValue);
+    // GM with checksumming off writes no header word (gm/sendFrag.cc:153-155, :219): the headers may be absent
+    const bool no_hdrs = mode == LAMPI_CSUM_NONE && hdr_kind == LAMPI_SEND_HDR_GM;
+    if (!d_hdrs && !no_hdrs) return to_int(hipErrorInvalidValue);
+    if (n == 0) return 0;
+    if (!d_frags || !d_msgs) return to_int(hipErrorInvalidValue);
+    int dev = 0;
+    hipError_t e = current_device(&dev);
+    if (e != hipSuccess) return to_int(e);
+    const uint32_t *img = nullptr;
+    e = device_tables(dev, &img);
+    if (e != hipSuccess) return to_int(e);
+    return to_int(launch_tmap_send_pack_batch(d_frags, n, d_msgs, nmsgs, max_len, (uint8_t *)d_hdrs, hdr_stride, hdr_kind,
+                                              mode, img, (hipStream_t)stream));
+}
+
+// The typemap receive step over fragment records (tmap_kernels.h: launch_tmap_recv_unpack_batch)
+int lampi_tmap_recv_unpack_batch(const lampi_tmap_frag *d_frags, size_t n, const lampi_tmap_msg *d_msgs, size_t nmsgs,
+                                 uint32_t max_len, const void *d_hdrs, size_t hdr_stride, int hdr_kind,
+                                 int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask, uint32_t *d_data_mask,
+                                 uint32_t *d_nbad, int mode, void *stream) {
+    if (!tmap_batch_args_ok(n, nmsgs, max_len, d_hdrs, hdr_stride, hdr_kind, mode)) return to_int(hipErrorInvalidValue);
+    // (checksumming off: no header is read)
+    if (!d_hdrs && mode != LAMPI_CSUM_NONE) return to_int(hipErrorInvalidValue);
+    if (!d_nbad || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask) return to_int(hipErrorInvalidValue);
+    if (n && (!d_frags || !d_msgs)) return to_int(hipErrorInvalidValue);
+    int dev = 0;
+    hipError_t e = current_device(&dev);
+    if (e != hipSuccess) return to_int(e);
+    const uint32_t *img = nullptr;
+    e = device_tables(dev, &img);
+    if (e != hipSuccess) return to_int(e);
+    return to_int(launch_tmap_recv_unpack_batch(d_frags, n, d_msgs, nmsgs, max_len, (const uint8_t *)d_hdrs, hdr_stride,
+                                                hdr_kind, d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode, img,
+                                                (hipStream_t)stream));
+}
+
 int lampi_chain_csum_batch_strided(const lampi_copy_desc *d_pieces, size_t npieces, const uint32_t *d_first,
                                    size_t nfrags, void *d_out, size_t out_stride, int mode, void *stream) {
     if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)

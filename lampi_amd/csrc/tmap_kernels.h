@@ -26,6 +26,14 @@
 // of at most kTmapLdsPairs pairs are staged in LDS beside the tables (40,640 bytes with them: four workgroups per
 // CU still fit); longer ones are read through L2.  A chunk wholly inside one piece moves as one 16-byte access;
 // otherwise piece by piece in 8-, 4-, 2- and 1-byte accesses, never touching a byte outside the pieces.
+//
+// Descriptor forms (lampi_tmap_send_pack_batch, lampi_tmap_recv_unpack_batch).  The same rows with the fragment
+// resolved from a record instead of from arithmetic on pack_off: the wave reads its lampi_tmap_frag and that
+// record's lampi_tmap_msg as wave-uniform values, tests them (tmap_record: the host never saw the tables) and runs
+// the frame, locate, tmap_move and checksum code above unchanged; R = max(1, ceil(max_len / 4096)) for every
+// fragment of the call.  The four waves of a workgroup may name four messages, so the typemap is staged only when
+// the workgroup's items share one message entry of at most kTmapLdsPairs pairs; otherwise it is read through L2 by
+// the same TmapView -- no LDS added, four workgroups per CU as before.
 
 namespace {
 
@@ -121,7 +129,29 @@ struct TmapJob {
     uint64_t seq0, app_len;       //          dataSeqOffset of packed byte 0; count * packed_size
     const uint32_t *img;
     uint32_t *rows;   // row values: [f] when R == 1, else [f * R + r] for the join
+    // the descriptor form: fragment f = frags[f] of the message msgs[frags[f].msg], whose typemap, base and
+    // app_len replace the fields above; R rows from max_len; rec null with checksumming off (no header is tested)
+    const lampi_tmap_frag *frags;
+    const lampi_tmap_msg *msgs;
+    uint32_t nmsgs, max_len;
 };
+
+// The descriptor form's record f with its message entry, tested before anything is computed from it (the tables
+// are device memory the host never saw): false for msg >= nmsgs, length > max_len (the frame holds max_len bytes),
+// an entry without pairs or with packed_size 0 (the rows divide by it) and, on send, a window past the message.
+__device__ __forceinline__ bool tmap_record(const lampi_tmap_frag *__restrict__ frags,
+                                            const lampi_tmap_msg *__restrict__ msgs, uint32_t nmsgs, uint32_t max_len,
+                                            size_t f, bool send, lampi_tmap_frag &fr, lampi_tmap_msg &m) {
+    fr = frags[f];
+    if (fr.msg >= nmsgs || fr.length > max_len) return false;
+    m = msgs[fr.msg];
+    if (!m.d_pairs || m.num_pairs == 0u || m.packed_size == 0u) return false;
+    if (send) {
+        const uint64_t total = m.count * m.packed_size;
+        if (fr.pack_off > total || fr.length > total - fr.pack_off) return false;
+    }
+    return true;
+}
 
 // The typemap's fields (k = 0 size, 1 offset, 2 seq_offset of pair i), from LDS when staged
 struct TmapView {
@@ -179,17 +209,71 @@ __device__ __forceinline__ void tmap_move(const TmapJob &J, const TmapView &tm, 
 }
 
 // One (fragment, row) per wave: item = item0 + 4 * blockIdx.x + wave.  kMode: lampi_csum_mode; kRecv: the receive
-// step (slot -> typemap) instead of the send step (typemap -> slot).
-template <int kMode, bool kRecv>
-__global__ void __launch_bounds__(256) tmap_row_kernel(const TmapJob J, size_t item0) {
+// step (slot -> typemap) instead of the send step (typemap -> slot).  kDesc: the descriptor form -- the wave's
+// fragment, typemap and base come from its record and that record's message entry (wave-uniform loads), tested by
+// tmap_record first; an invalid record's rows run as a dropped fragment's (nothing read, nothing written, row
+// value 0).  The typemap is staged in LDS when every item of the workgroup names the same message entry and that
+// has at most kTmapLdsPairs pairs; a workgroup whose waves name different messages reads them through L2 (no LDS
+// added: four workgroups per CU as before).
+template <int kMode, bool kRecv, bool kDesc = false>
+__global__ void __launch_bounds__(256) tmap_row_kernel(const TmapJob Ja, size_t item0) {
     constexpr bool kCrc = kMode == LAMPI_CSUM_CRC32, kSum = kMode == LAMPI_CSUM_SUM32;
     __shared__ __attribute__((aligned(16))) uint32_t lds[kCrc ? kLtBytes / 4 : 4];
     __shared__ uint64_t tml[3 * kTmapLdsPairs];
+    TmapJob J = Ja;
     const uint32_t t = threadIdx.x, lane = t & 63u;
-    const size_t item = item0 + (size_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(t >> 6);
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    const size_t item = item0 + (size_t)blockIdx.x * 4 + wv;
     const bool in = item < J.nitems;
-    const size_t f = in ? item / J.R : 0;
-    const uint32_t r = in ? (uint32_t)(item - f * J.R) : 0u;
+    size_t f = 0;
+    uint32_t r = 0;
+    bool ok = true;          // (descriptor form: the record is valid)
+    bool stage_desc = false; //  ... and the workgroup's items share one typemap that fits the LDS
+    lampi_tmap_frag fr{};
+    if constexpr (!kDesc) {
+        f = in ? item / J.R : 0;
+        r = in ? (uint32_t)(item - f * J.R) : 0u;
+    } else {
+        // the workgroup's first item is always inside; the others' fragments follow from it without dividing again
+        const size_t wg0 = item0 + (size_t)blockIdx.x * 4;
+        const size_t f0 = wg0 / J.R;
+        const uint32_t r0 = (uint32_t)(wg0 - f0 * J.R);
+        const uint32_t m0 = J.frags[f0].msg;
+        bool same = m0 < J.nmsgs;
+        for (uint32_t w = 1; w < 4u; ++w) {
+            size_t fw = f0;
+            uint32_t rw = r0 + w;
+            while (rw >= J.R) rw -= J.R, ++fw;
+            if (wg0 + w < J.nitems && J.frags[fw].msg != m0) same = false;
+            if (w == wv) f = fw, r = rw;
+        }
+        if (wv == 0u) f = f0, r = r0;
+        if (!in) f = 0, r = 0u;
+        J.pairs = nullptr;
+        J.num_pairs = 0u;
+        J.packed_size = J.extent = 0u;
+        J.base = nullptr;
+        J.app_len = 0u;
+        if (same) {  // (workgroup-uniform: every wave read the same records)
+            const lampi_tmap_msg &e0 = J.msgs[m0];
+            const lampi_tmap_elt *p0 = e0.d_pairs;
+            const uint32_t np0 = e0.num_pairs;
+            if (p0 && np0 >= 1u && np0 <= kTmapLdsPairs) {
+                stage_desc = true;
+                if (t < 3u * np0) tml[t] = ((gu64 *)(uintptr_t)p0)[t];
+            }
+        }
+        lampi_tmap_msg m{};
+        ok = in && tmap_record(J.frags, J.msgs, J.nmsgs, J.max_len, f, !kRecv, fr, m);
+        if (ok) {
+            J.pairs = m.d_pairs;
+            J.num_pairs = m.num_pairs;
+            J.packed_size = m.packed_size;
+            J.extent = m.extent;
+            J.base = (uint8_t *)(uintptr_t)m.base;
+            J.app_len = m.count * m.packed_size;
+        }
+    }
     // the tables' image loads first, as crc_light_copy_kernel
     constexpr uint32_t kNibPieces = kLightTables * kLightTableWords / 4;
     const uint32_t t2 = min(256u + t, kNibPieces - 1);
@@ -202,10 +286,22 @@ __global__ void __launch_bounds__(256) tmap_row_kernel(const TmapJob J, size_t i
             bs[i] = reinterpret_cast<const u32x4 *>(J.img + kImgSliceBasis)[((t & 7u) >> 1) * 4 + i];
     }
     // the fragment (wave-uniform): L bytes checksummed, the first ncopy of them moved, packed byte p0 its first
-    uint8_t *slot = J.ring + f * J.slot_stride;
+    uint8_t *slot = kDesc ? nullptr : J.ring + f * J.slot_stride;
     uint64_t p0 = 0;
     uint32_t L = 0, ncopy = 0;
-    if (in) {
+    if constexpr (kDesc) {
+        if (ok) {
+            p0 = fr.pack_off;
+            if constexpr (!kRecv) {
+                L = ncopy = fr.length;
+            } else {  // CopyToApp's rules, the length from the record
+                const bool pass = !J.rec || J.rec[f].ok != 0u;
+                const uint64_t room = p0 >= J.app_len ? 0u : J.app_len - p0;
+                ncopy = pass ? (uint32_t)min((uint64_t)fr.length, room) : 0u;
+                L = kMode == LAMPI_CSUM_NONE ? ncopy : (ncopy ? fr.length : 0u);
+            }
+        }
+    } else if (in) {
         if constexpr (!kRecv) {
             const uint64_t off = (uint64_t)f * J.frag_len;
             const uint64_t rem = J.pack_len > off ? J.pack_len - off : 0u;
@@ -224,10 +320,11 @@ __global__ void __launch_bounds__(256) tmap_row_kernel(const TmapJob J, size_t i
             p0 = off;
         }
     }
-    uint8_t *payload = slot + kSendHdrBytes;
-    const bool staged = J.num_pairs <= kTmapLdsPairs;
+    uint8_t *payload = kDesc ? (uint8_t *)(uintptr_t)fr.payload : slot + kSendHdrBytes;
+    const bool staged = kDesc ? stage_desc : J.num_pairs <= kTmapLdsPairs;
     if (staged) {
-        if (t < 3u * J.num_pairs) tml[t] = ((gu64 *)(uintptr_t)J.pairs)[t];
+        if constexpr (!kDesc)
+            if (t < 3u * J.num_pairs) tml[t] = ((gu64 *)(uintptr_t)J.pairs)[t];
         __syncthreads();
     }
     const TmapView tm{(gu64 *)(uintptr_t)J.pairs, tml, staged};
@@ -237,7 +334,7 @@ __global__ void __launch_bounds__(256) tmap_row_kernel(const TmapJob J, size_t i
     const uint64_t fa = max(fs, P), fb = min(fs + kRowBytes, P + L);
     const bool live = in && fb > fa;
     // (send, CRC: an empty fragment's last row still runs -- the register's image in its padding is the value)
-    const bool run = live || (kCrc && !kRecv && in && L == 0u && r == J.R - 1u);
+    const bool run = live || (kCrc && !kRecv && in && ok && L == 0u && r == J.R - 1u);
     uint64_t e0 = 0, r0 = 0;  // element and byte in it of the row's first byte
     if (live) {
         const uint64_t ps = p0 + (fa - P);
@@ -425,7 +522,7 @@ __global__ void __launch_bounds__(256) tmap_recv_verdict_kernel(const uint8_t *_
 
 // tmap_row_kernel over n fragments of R rows, then the join of their rows into vals (R > 1).  Launches of at most
 // 2^24 - 1 workgroups (a grid has under 2^32 threads).
-template <bool kRecv>
+template <bool kRecv, bool kDesc = false>
 hipError_t launch_tmap_rows(TmapJob J, size_t n, uint32_t *vals, int mode, hipStream_t s) {
     const bool none = mode == LAMPI_CSUM_NONE;
     uint32_t *rows = nullptr;
@@ -441,11 +538,11 @@ hipError_t launch_tmap_rows(TmapJob J, size_t n, uint32_t *vals, int mode, hipSt
     for (size_t item0 = 0; item0 < J.nitems; item0 += kMaxItems) {
         const dim3 grid((unsigned)((std::min(J.nitems - item0, kMaxItems) + 3) / 4));
         if (mode == LAMPI_CSUM_CRC32)
-            hipLaunchKernelGGL((tmap_row_kernel<LAMPI_CSUM_CRC32, kRecv>), grid, dim3(256), 0, s, J, item0);
+            hipLaunchKernelGGL((tmap_row_kernel<LAMPI_CSUM_CRC32, kRecv, kDesc>), grid, dim3(256), 0, s, J, item0);
         else if (mode == LAMPI_CSUM_SUM32)
-            hipLaunchKernelGGL((tmap_row_kernel<LAMPI_CSUM_SUM32, kRecv>), grid, dim3(256), 0, s, J, item0);
+            hipLaunchKernelGGL((tmap_row_kernel<LAMPI_CSUM_SUM32, kRecv, kDesc>), grid, dim3(256), 0, s, J, item0);
         else
-            hipLaunchKernelGGL((tmap_row_kernel<LAMPI_CSUM_NONE, kRecv>), grid, dim3(256), 0, s, J, item0);
+            hipLaunchKernelGGL((tmap_row_kernel<LAMPI_CSUM_NONE, kRecv, kDesc>), grid, dim3(256), 0, s, J, item0);
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && rows) {
@@ -458,6 +555,79 @@ hipError_t launch_tmap_rows(TmapJob J, size_t n, uint32_t *vals, int mode, hipSt
         e = hipGetLastError();
     }
     return rows ? scratch_done(s, rows, pooled, e) : e;
+}
+
+// The descriptor form's stamp: send_stamp_kernel<false>'s route (the prefix read from the header, on the LDS
+// slice tables) with fragment i's emptiness taken from its record; an invalid record's header stays as it is.
+__global__ void __launch_bounds__(256) tmap_send_stamp_kernel(uint8_t *hdrs, size_t stride, uint32_t n,
+                                                              const uint32_t *__restrict__ vals,
+                                                              const lampi_tmap_frag *__restrict__ frags,
+                                                              const lampi_tmap_msg *__restrict__ msgs, uint32_t nmsgs,
+                                                              uint32_t max_len, int kind, int mode,
+                                                              const uint32_t *__restrict__ img) {
+    __shared__ uint32_t S[1024];
+    if (mode == LAMPI_CSUM_CRC32) stage_slices(S, img);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    lampi_tmap_frag fr;
+    lampi_tmap_msg m;
+    if (!tmap_record(frags, msgs, nmsgs, max_len, i, true, fr, m)) return;
+    uint8_t *h = hdrs + (size_t)i * stride;
+    if (mode == LAMPI_CSUM_NONE) {
+        send_stamp(h, 0u, true, kind, mode, 0u);
+        return;
+    }
+    send_stamp(h, vals[i], fr.length == 0u, kind, mode, send_hdr_prefix(h, mode, SliceLds{S}));
+}
+
+// The descriptor form's verdicts: tmap_recv_verdict_kernel with pack_off, length and the message from the
+// records; an invalid record is a dropped fragment in every mode (rec null: checksumming off, every header passes).
+__global__ void __launch_bounds__(256) tmap_batch_verdict_kernel(const lampi_tmap_frag *__restrict__ frags, uint32_t n,
+                                                                 const lampi_tmap_msg *__restrict__ msgs,
+                                                                 uint32_t nmsgs, uint32_t max_len,
+                                                                 const RecvHdrRec *__restrict__ rec,
+                                                                 const uint32_t *__restrict__ vals, int mode,
+                                                                 int64_t *copied, uint32_t *csum, uint32_t *hmask,
+                                                                 uint32_t *dmask, uint32_t *nbad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    lampi_tmap_frag fr;
+    lampi_tmap_msg m;
+    const bool valid = tmap_record(frags, msgs, nmsgs, max_len, i, false, fr, m);
+    RecvHdrRec rc{1u, 0u};
+    if (rec) rc = rec[i];
+    if (!valid || !rc.ok) {
+        copied[i] = (int64_t)LAMPI_RECV_HDR_BAD;
+        csum[i] = 0u;
+        atomicOr(hmask + (i >> 5), 1u << (i & 31u));
+        atomicAdd(nbad, 1u);
+        return;
+    }
+    const uint64_t app_len = m.count * m.packed_size;
+    const uint64_t room = fr.pack_off >= app_len ? 0u : app_len - fr.pack_off;
+    const uint32_t c = (uint32_t)min((uint64_t)fr.length, room);
+    const bool none = mode == LAMPI_CSUM_NONE;
+    const uint32_t v = none ? 0u : c ? vals[i] : mode == LAMPI_CSUM_CRC32 ? kCrcInit : 0u;
+    const bool bad = !none && c != 0u && v != rc.expected;
+    csum[i] = v;
+    copied[i] = bad ? (int64_t)LAMPI_RECV_DATA_BAD : (int64_t)c;
+    if (bad) {
+        atomicOr(dmask + (i >> 5), 1u << (i & 31u));
+        atomicAdd(nbad + 1, 1u);
+    }
+}
+
+// The descriptor form's job: no ring, no single typemap -- the records and the message table, R from max_len
+TmapJob tmap_batch_job(const lampi_tmap_frag *frags, const lampi_tmap_msg *msgs, size_t nmsgs, uint32_t max_len,
+                       const uint32_t *img) {
+    TmapJob J{};
+    J.R = (uint32_t)std::max<size_t>(1, ((size_t)max_len + kRowBytes - 1) / kRowBytes);
+    J.frags = frags;
+    J.msgs = msgs;
+    J.nmsgs = (uint32_t)nmsgs;
+    J.max_len = max_len;
+    J.img = img;
+    return J;
 }
 
 TmapJob tmap_job(const lampi_tmap &tm, uint8_t *base, uint8_t *ring, size_t slot_stride, size_t payload_room,
@@ -544,6 +714,64 @@ hipError_t launch_tmap_recv_unpack(const uint8_t *ring, size_t nslots, size_t sl
             hipLaunchKernelGGL(tmap_recv_verdict_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s, ring,
                                slot_stride, (uint32_t)nslots, (const RecvHdrRec *)rec, (const uint32_t *)vals, seq0,
                                J.app_len, mode, copied, csum, hmask, dmask, nbad);
+            e = hipGetLastError();
+        }
+    }
+    return scratch_done(s, buf, pooled, e);
+}
+
+// The send step over fragment records (lampi_tmap_send_pack_batch): the rows of every record gather its window
+// through its own message's typemap, then tmap_send_stamp_kernel stamps the headers the caller prefilled (GM with
+// checksumming off writes no header word: no stamp launch, hdrs may be null).
+hipError_t launch_tmap_send_pack_batch(const lampi_tmap_frag *frags, size_t n, const lampi_tmap_msg *msgs, size_t nmsgs,
+                                       uint32_t max_len, uint8_t *hdrs, size_t hdr_stride, int kind, int mode,
+                                       const uint32_t *img, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (!img) return hipErrorInvalidValue;
+    uint32_t *vals = nullptr;
+    bool pooled = false;
+    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    if (e != hipSuccess) return e;
+    e = launch_tmap_rows<false, true>(tmap_batch_job(frags, msgs, nmsgs, max_len, img), n, vals, mode, s);
+    if (e == hipSuccess && !(mode == LAMPI_CSUM_NONE && kind == LAMPI_SEND_HDR_GM)) {
+        hipLaunchKernelGGL(tmap_send_stamp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs, hdr_stride,
+                           (uint32_t)n, (const uint32_t *)vals, frags, msgs, (uint32_t)nmsgs, max_len, kind, mode, img);
+        e = hipGetLastError();
+    }
+    return scratch_done(s, vals, pooled, e);
+}
+
+// The receive step over fragment records (lampi_tmap_recv_unpack_batch): the verdicts zeroed, recv_hdr_test_kernel
+// over the headers (no length limit of its own: the record's length counts; not run with checksumming off, when no
+// header is read), the rows of the valid records that passed, their join, and one verdict launch.
+hipError_t launch_tmap_recv_unpack_batch(const lampi_tmap_frag *frags, size_t n, const lampi_tmap_msg *msgs,
+                                         size_t nmsgs, uint32_t max_len, const uint8_t *hdrs, size_t hdr_stride,
+                                         int kind, int64_t *copied, uint32_t *csum, uint32_t *hmask, uint32_t *dmask,
+                                         uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s) {
+    if (n == 0) return hipMemsetAsync(nbad, 0, 2 * sizeof(uint32_t), s);
+    if (!img) return hipErrorInvalidValue;
+    hipError_t e = zero_verdicts2(hmask, dmask, n, nbad, s);
+    if (e != hipSuccess) return e;
+    uint32_t *buf = nullptr;  // the records (two words a fragment), then the fragments' values
+    bool pooled = false;
+    e = stream_vals(s, 3 * n, &buf, &pooled);
+    if (e != hipSuccess) return e;
+    const bool none = mode == LAMPI_CSUM_NONE;
+    RecvHdrRec *rec = none ? nullptr : (RecvHdrRec *)buf;
+    uint32_t *vals = buf + 2 * n;
+    if (!none) {
+        hipLaunchKernelGGL(recv_hdr_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs, hdr_stride,
+                           (uint32_t)n, kind, mode, 0xFFFFFFFFu, img, rec);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        TmapJob J = tmap_batch_job(frags, msgs, nmsgs, max_len, img);
+        J.rec = rec;
+        e = launch_tmap_rows<true, true>(J, n, vals, mode, s);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(tmap_batch_verdict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, frags,
+                               (uint32_t)n, msgs, (uint32_t)nmsgs, max_len, (const RecvHdrRec *)rec,
+                               (const uint32_t *)vals, mode, copied, csum, hmask, dmask, nbad);
             e = hipGetLastError();
         }
     }

@@ -14,6 +14,7 @@ from ._lib import (BY_BYTES, CRC32, CRC_INITIAL_REGISTER, HDR_GM, HDR_IB, HDR_QU
 
 __all__ = ["CRC32", "SUM32", "NONE", "HDR_GM", "HDR_IB", "HDR_QUADRICS", "RECV_DATA_BAD", "RECV_HDR_BAD", "recv_unpack_batch", "msg_recv_unpack",
            "make_tmap", "tmap_send_pack", "tmap_recv_unpack",
+           "make_tmap_msgs", "make_tmap_frags", "tmap_send_pack_batch", "tmap_recv_unpack_batch",
            "send_pack_batch", "msg_send_pack","chain_copy_to_app_batch", "frag_bcopy_batch_strided", "msg_bcopy_strided",
            "chain_csum_batch_strided", "header_csum_batch_strided", "frag_csum_batch", "diag_frag_csum_batch_per_wave", "frag_csum64_batch", "frag_bcopy_batch", "msg_bcopy", "msg_csum", "fill_stream", "fill_stream_frags",
            "make_descs", "make_copy_descs", "as_u32", "chain_csum_batch", "header_csum_batch", "header_check_batch", "check_data_batch",
@@ -738,6 +739,111 @@ def tmap_recv_unpack(ring: torch.Tensor, nslots: int, slot_stride: int, base: to
                                        ctypes.addressof(tmap.struct), seq_offset0 & (2**64 - 1), copied.data_ptr(),
                                        csum.data_ptr(), hmask.data_ptr(), dmask.data_ptr(), nbad.data_ptr(), mode,
                                        _stream_handle(stream)), "lampi_tmap_recv_unpack")
+    return copied[:count], csum[:count], hmask, dmask, nbad
+
+
+class TmapMsgs:
+    """The descriptor forms' message table on the device (make_tmap_msgs): ``table`` is the array of
+    ``lampi_tmap_msg`` (int64 [nmsgs, 8] storage); the pair tensors its d_pairs point into and the tensors its bases
+    point into are kept alive here beside it."""
+
+    def __init__(self, table: torch.Tensor, tmaps: list, bases: list):
+        self.table, self.tmaps, self.bases = table, tmaps, bases
+        self.pairs = [t.pairs for t in tmaps]
+
+    def __len__(self) -> int:
+        return self.table.shape[0]
+
+
+def make_tmap_msgs(entries, device) -> TmapMsgs:
+    """Build the message table of tmap_send_pack_batch / tmap_recv_unpack_batch: ``entries`` is a list of
+    (DeviceTmap, base tensor, base_offset) -- message k's typemap and element count, and byte ``base_offset`` of
+    ``base`` as the datatype's origin; every piece must lie inside its tensor."""
+    host = np.zeros((len(entries), 8), dtype=np.uint64)
+    tmaps, bases = [], []
+    for k, (tmap, base, base_offset) in enumerate(entries):
+        addr = _tmap_base(base, int(base_offset), tmap)
+        host[k, 0] = tmap.pairs.data_ptr()
+        host[k, 1], host[k, 2], host[k, 3] = tmap.extent, tmap.packed_size, tmap.count
+        host[k, 4] = tmap.num_pairs  # (reserved @36 = 0)
+        host[k, 5] = addr
+        tmaps.append(tmap)
+        bases.append(base)
+    return TmapMsgs(torch.from_numpy(host.view(np.int64)).to(device), tmaps, bases)
+
+
+def make_tmap_frags(payload_addr, pack_off, length, msg, device) -> torch.Tensor:
+    """Build a device array of ``lampi_tmap_frag`` (n x 32 bytes, int64 [n, 4] storage): fragment i = ``length[i]``
+    packed bytes from packed byte ``pack_off[i]`` of message ``msg[i]`` of the table, its payload at the device
+    address ``payload_addr[i]``."""
+    pa = np.asarray(payload_addr, dtype=np.uint64)
+    po = np.asarray(pack_off, dtype=np.uint64)
+    ln = np.asarray(length, dtype=np.uint64)
+    mi = np.asarray(msg, dtype=np.uint64)
+    n = pa.size
+    if not (po.size == ln.size == mi.size == n):
+        raise ValueError("record fields differ in size")
+    if n and (int(ln.max()) > 0xFFFFFFFF or int(mi.max()) > 0xFFFFFFFF):
+        raise ValueError("length and msg are 32-bit fields")
+    host = np.zeros((n, 4), dtype=np.uint64)
+    host[:, 0], host[:, 1] = pa, po
+    host[:, 2] = ln | (mi << np.uint64(32))
+    return torch.from_numpy(host.view(np.int64)).to(device)
+
+
+def _tmap_batch_args(frags: torch.Tensor, msgs, n, hdrs, hdr_stride: int, offset: int):
+    _require_cuda(frags, "frags")
+    table = msgs.table if isinstance(msgs, TmapMsgs) else msgs
+    _require_cuda(table, "msgs")
+    count = frags.numel() * frags.element_size() // 32 if n is None else int(n)
+    if count * 32 > frags.numel() * frags.element_size():
+        raise ValueError("n exceeds the record tensor")
+    ptr = None
+    if hdrs is not None:
+        _require_cuda(hdrs, "hdrs")
+        if count and offset + (count - 1) * hdr_stride + SEND_HDR_BYTES > hdrs.numel() * hdrs.element_size():
+            raise ValueError(f"hdrs is too small for {count} headers of stride {hdr_stride}")
+        ptr = hdrs.data_ptr() + offset
+    return table, table.numel() * table.element_size() // 64, count, ptr
+
+
+def tmap_send_pack_batch(frags: torch.Tensor, msgs, max_len: int, hdrs: torch.Tensor | None, hdr_stride: int,
+                         offset: int = 0, kind: int = HDR_GM, mode: int = CRC32, n: int | None = None,
+                         stream: torch.cuda.Stream | None = None) -> torch.Tensor | None:
+    """send_pack_batch through typemaps, for the fragments of several messages in one call: record i
+    (make_tmap_frags) names its message in ``msgs`` (make_tmap_msgs), its window [pack_off, pack_off + length) of
+    that message's packed bytes and the payload address they are gathered to; header i -- 72 bytes at byte offset +
+    i*hdr_stride of ``hdrs``, bytes [0, 64) already filled -- gets dataChecksum @64 and the header checksum @68 of
+    ``kind`` (HDR_GM / HDR_IB).  ``max_len``: an upper bound on every record's length (it fixes the rows per
+    fragment; batch by size class).  A record that is invalid (msg outside the table, length > max_len, an entry
+    without pairs, a window past the message) is skipped.  ``hdrs`` may be None only for HDR_GM with mode NONE;
+    returns ``hdrs``."""
+    if hdrs is None and not (kind == HDR_GM and mode == NONE):
+        raise ValueError("hdrs is required unless kind is HDR_GM and mode is NONE")
+    table, nmsgs, count, ptr = _tmap_batch_args(frags, msgs, n, hdrs, hdr_stride, offset)
+    check(lib().lampi_tmap_send_pack_batch(frags.data_ptr(), count, table.data_ptr(), nmsgs, int(max_len), ptr,
+                                           hdr_stride, kind, mode, _stream_handle(stream)),
+          "lampi_tmap_send_pack_batch")
+    return hdrs
+
+
+def tmap_recv_unpack_batch(frags: torch.Tensor, msgs, max_len: int, hdrs: torch.Tensor | None, hdr_stride: int,
+                           offset: int = 0, kind: int = HDR_GM, mode: int = CRC32,
+                           stream: torch.cuda.Stream | None = None, n: int | None = None):
+    """recv_unpack_batch through typemaps, for the drained fragments of several posted receives in one call: header
+    i is tested as ``kind`` says; a fragment that passes is delivered through its own message's typemap -- the
+    first min(length, count * packed_size - pack_off) packed bytes at its payload address scattered to their
+    pieces, all ``length`` bytes checksummed against the word @64.  A failed header or an invalid record (as for
+    tmap_send_pack_batch, without the window test) drops the fragment as RECV_HDR_BAD.  Returns (copied, csum,
+    hdr_mask, data_mask, nbad) as recv_unpack_batch.  ``hdrs`` may be None with mode NONE (no header is read)."""
+    if hdrs is None and mode != NONE:
+        raise ValueError("hdrs is required unless mode is NONE (checksumming off)")
+    table, nmsgs, count, ptr = _tmap_batch_args(frags, msgs, n, hdrs, hdr_stride, offset)
+    copied, csum, hmask, dmask, nbad = _unpack_out(count, frags.device)
+    check(lib().lampi_tmap_recv_unpack_batch(frags.data_ptr(), count, table.data_ptr(), nmsgs, int(max_len), ptr,
+                                             hdr_stride, kind, copied.data_ptr(), csum.data_ptr(), hmask.data_ptr(),
+                                             dmask.data_ptr(), nbad.data_ptr(), mode, _stream_handle(stream)),
+          "lampi_tmap_recv_unpack_batch")
     return copied[:count], csum[:count], hmask, dmask, nbad
 
 
