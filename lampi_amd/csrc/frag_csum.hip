@@ -76,10 +76,16 @@ static int knob_waves(const char *e, int dflt) {
 }
 
 // per-stream device scratch (defined with the launchers)
-static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, bool *pooled);
-static hipError_t scratch_done(hipStream_t s, void *p, bool pooled, hipError_t e);
+static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out);
 static hipError_t pair_counters(hipStream_t s, uint32_t **cur, uint32_t **next);
 static void reset_pair_counters(hipStream_t s);
+
+// One thread per item: kernel over n items in workgroups of 256 threads on s.
+template <class Kernel, class... Args>
+static hipError_t launch_per_item(Kernel kernel, size_t n, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, args...);
+    return hipGetLastError();
+}
 
 namespace {
 
@@ -3396,13 +3402,12 @@ static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uin
     uint32_t *left = nullptr, *next_left = nullptr, *list = nullptr;
     static const int kWv = knob_waves(LAMPI_AB_ENV("LAMPI_PAIR_WAVES"), 8);
     const size_t nwg = (n + 2 * kWv - 1) / (2 * kWv);
-    bool pooled = false;
     // (one entry per wave at most: a batch whose shape changed since the census leaves every wave)
-    hipError_t e = stream_scratch(s, nwg * kWv * sizeof(uint32_t), (void **)&list, &pooled);
+    hipError_t e = stream_scratch(s, nwg * kWv * sizeof(uint32_t), (void **)&list);
     if (e != hipSuccess) return e;
     // the counter pair is taken only now: a failure before this point leaves it untouched
     e = pair_counters(s, &left, &next_left);
-    if (e != hipSuccess) return scratch_done(s, list, pooled, e);
+    if (e != hipSuccess) return e;
     with_waves(kWv, [&](auto wv) {
         constexpr int kW = decltype(wv)::value;
         hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, kW>), dim3((unsigned)nwg), dim3(64 * kW), 0, s, src, n, img,
@@ -3416,7 +3421,7 @@ static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uin
     }
     // a launch that failed left a counter unzeroed (the leftover kernel zeroes the next call's): zero both
     if (e != hipSuccess) reset_pair_counters(s);
-    return scratch_done(s, list, pooled, e);
+    return e;
 }
 
 // waves per workgroup of the table-light copy kernels: four (the copy shape, four 36 KiB workgroups per CU).
@@ -3454,19 +3459,16 @@ static hipError_t launch_crc_light_frag_copy(const Src &src, size_t n, const uin
         return hipGetLastError();
     }
     uint32_t *groups = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_scratch(s, n * W * sizeof(uint32_t), (void **)&groups, &pooled);
+    hipError_t e = stream_scratch(s, n * W * sizeof(uint32_t), (void **)&groups);
     if (e != hipSuccess) return e;
     launch(n * W, groups);
     e = hipGetLastError();
     if (e == hipSuccess) {
         uint32_t G = 1;
         while (G < W && G < 64u) G <<= 1;
-        hipLaunchKernelGGL(crc_light_group_join_kernel<Src>, dim3((unsigned)((n * G + 255) / 256)), dim3(256), 0, s, src,
-                           n, W, G, groups, out);
-        e = hipGetLastError();
+        e = launch_per_item(crc_light_group_join_kernel<Src>, n * G, s, src, n, W, G, groups, out);
     }
-    return scratch_done(s, groups, pooled, e);
+    return e;
 }
 
 // ---- CRC fast path: regular batches -------------------------------------------------------
@@ -5261,11 +5263,11 @@ ScratchTable::~ScratchTable() {
 }  // namespace
 
 // (vals: the slot's second buffer, at least 64 KiB, instead of its first, at least 1 MiB)
-static hipError_t stream_buffer(hipStream_t s, size_t bytes, void **out, bool *pooled, bool vals) {
+// (nothing for the caller to release: every buffer stays with the thread's table)
+static hipError_t stream_buffer(hipStream_t s, size_t bytes, void **out, bool vals) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     hipError_t ce = hipStreamIsCapturing(s, &cs);
     if (ce != hipSuccess) return ce;
-    *pooled = false;  // (nothing for scratch_done to release: every buffer stays with the thread's table)
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -5310,14 +5312,14 @@ static hipError_t stream_buffer(hipStream_t s, size_t bytes, void **out, bool *p
     return hipSuccess;
 }
 
-static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, bool *pooled) {
-    return stream_buffer(s, bytes, out, pooled, false);
+static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out) {
+    return stream_buffer(s, bytes, out, false);
 }
 
 // n checksum words that outlive the launchers filling them (which take stream_scratch themselves): the slot's
 // second buffer, pooled the same way -- no hipMallocAsync / hipFreeAsync pair in the stream.
-static hipError_t stream_vals(hipStream_t s, size_t n, uint32_t **out, bool *pooled) {
-    return stream_buffer(s, std::max<size_t>(n, 1) * sizeof(uint32_t), (void **)out, pooled, true);
+static hipError_t stream_vals(hipStream_t s, size_t n, uint32_t **out) {
+    return stream_buffer(s, std::max<size_t>(n, 1) * sizeof(uint32_t), (void **)out, true);
 }
 
 // The pair kernel's leftover counters for stream s (this thread's): two, zeroed on the stream when created;
@@ -5380,11 +5382,6 @@ void release_thread_scratch() {
 }
 
 int64_t device_scratch_bytes() { return g_scratch_bytes.load(std::memory_order_relaxed); }
-
-static hipError_t scratch_done(hipStream_t s, void *p, bool pooled, hipError_t e) {
-    const hipError_t f = pooled ? hipFreeAsync(p, s) : hipSuccess;
-    return e != hipSuccess ? e : f;
-}
 
 // ---- Batch shapes learned on the device ----------------------------------------------------------
 // A descriptor batch's lengths live on the device, so the host cannot size a one-row-per-wave grid for
@@ -5590,8 +5587,7 @@ static hipError_t launch_planned(const lampi_frag_desc *d, size_t n, uint32_t *o
     const size_t gmax = 2 + (cap + kPlanF - 1) / kPlanF + gb;                             // workgroups at most
     const size_t seg_bytes = (cap * sizeof(SegDesc) + 255) & ~(size_t)255;
     uint8_t *scratch = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_scratch(s, seg_bytes + (gmax + 2) * sizeof(uint32_t), (void **)&scratch, &pooled);
+    hipError_t e = stream_scratch(s, seg_bytes + (gmax + 2) * sizeof(uint32_t), (void **)&scratch);
     if (e != hipSuccess) return e;
     SegDesc *segs = (SegDesc *)scratch;
     uint32_t *plan = (uint32_t *)(scratch + seg_bytes);
@@ -5610,7 +5606,7 @@ static hipError_t launch_planned(const lampi_frag_desc *d, size_t n, uint32_t *o
                            dim3(64 * kWv), 0, s, SegSource{segs, d}, cap, 0u, img, out, (const uint32_t *)plan);
         e = hipGetLastError();
     }
-    return scratch_done(s, scratch, pooled, e);
+    return e;
 }
 
 // LAMPI_CSUM_ROWS_HINT(r) on a read-only descriptor batch (fragments of about r rows): the count split
@@ -5690,11 +5686,10 @@ static hipError_t launch_crc_desc_whole(const lampi_frag_desc *d, size_t n, uint
     }
     if (fpw > (R == 1 ? 32u : 64u)) return hipErrorInvalidValue;  // (a wave's descriptors live in its 64 lanes)
     uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_scratch(s, (items + 1) * sizeof(uint32_t), (void **)&list, &pooled);
+    hipError_t e = stream_scratch(s, (items + 1) * sizeof(uint32_t), (void **)&list);
     if (e != hipSuccess) return e;
     e = pair_counters(s, &left, &next_left);
-    if (e != hipSuccess) return scratch_done(s, list, pooled, e);
+    if (e != hipSuccess) return e;
     if (R == 1)
         hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, false, kWaves, 0, true>),
                            grid_for(items, fpw), dim3(kBlock), 0, s, reinterpret_cast<const uint8_t *>(d),
@@ -5711,7 +5706,6 @@ static hipError_t launch_crc_desc_whole(const lampi_frag_desc *d, size_t n, uint
         e = hipGetLastError();
     }
     if (e != hipSuccess) reset_pair_counters(s);
-    e = scratch_done(s, list, pooled, e);
     if (e == hipSuccess && R == 1 && (n & 1u))
         e = launch_crc_light_frag_copy(DescSource{d + n - 1}, 1, img, out + n - 1, s);
     return e;
@@ -5738,11 +5732,10 @@ static hipError_t launch_desc_packed(const lampi_frag_desc *d, size_t n, uint32_
     const size_t F = 2 * kRowBytes / L, nv = n / F;
     if (nv * 2 < kPackedMinRows || nv > 0xFFFFFFFFull || nv * F / 2 > 0xFFFFFFFFull) return hipSuccess;
     uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_scratch(s, (nv * F / 2 + 1) * sizeof(uint32_t), (void **)&list, &pooled);
+    hipError_t e = stream_scratch(s, (nv * F / 2 + 1) * sizeof(uint32_t), (void **)&list);
     if (e != hipSuccess) return e;
     e = pair_counters(s, &left, &next_left);
-    if (e != hipSuccess) return scratch_done(s, list, pooled, e);
+    if (e != hipSuccess) return e;
     switch (L) {
         case 64: e = launch_packed_desc_k<kSum, 1>(d, nv, out, img, s, list, left); break;
         case 128: e = launch_packed_desc_k<kSum, 2>(d, nv, out, img, s, list, left); break;
@@ -5762,7 +5755,6 @@ static hipError_t launch_desc_packed(const lampi_frag_desc *d, size_t n, uint32_
         e = hipGetLastError();
     }
     if (e != hipSuccess) reset_pair_counters(s);
-    e = scratch_done(s, list, pooled, e);
     if (e == hipSuccess) *done = nv * F;
     return e;
 }
@@ -5775,11 +5767,10 @@ static hipError_t launch_sum_desc_row4k(const lampi_frag_desc *d, size_t n, uint
     const size_t F = kRowBytes / L, nrow = n / F;
     if (!row4k_rows(nrow) || nrow * F > 0xFFFFFFFFull) return hipSuccess;
     uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_scratch(s, (nrow * F + 1) * sizeof(uint32_t), (void **)&list, &pooled);
+    hipError_t e = stream_scratch(s, (nrow * F + 1) * sizeof(uint32_t), (void **)&list);
     if (e != hipSuccess) return e;
     e = pair_counters(s, &left, &next_left);
-    if (e != hipSuccess) return scratch_done(s, list, pooled, e);
+    if (e != hipSuccess) return e;
     with_row4k_lanes(L, [&](auto kG) {
         hipLaunchKernelGGL(sum_row4k_desc_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0, s, d, img,
                            out, list, left);
@@ -5791,7 +5782,6 @@ static hipError_t launch_sum_desc_row4k(const lampi_frag_desc *d, size_t n, uint
         e = hipGetLastError();
     }
     if (e != hipSuccess) reset_pair_counters(s);
-    e = scratch_done(s, list, pooled, e);
     if (e == hipSuccess) *done = nrow * F;
     return e;
 }
@@ -5809,7 +5799,7 @@ static hipError_t launch_sum_desc_row4k(const lampi_frag_desc *d, size_t n, uint
 // target (0: the count split).
 static uint32_t small_batch_groups(size_t n, hipStream_t s) {
     static const size_t target = knob_size(LAMPI_AB_ENV("LAMPI_SMALL_BATCH"), (size_t)4096);
-    // graph captures keep the count split: the groups' scratch would be a pooled allocation inside the graph
+    // graph captures keep the count split: the groups' scratch would be one more buffer held for the graph
     // (bench.py --latency: a replayed one-descriptor call 6.9 -> 32 us)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return 1u;
@@ -6100,8 +6090,7 @@ static hipError_t launch_sum_copy_groups(const Src &src, size_t n, uint32_t *out
         return hipGetLastError();
     }
     uint32_t *groups = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_scratch(s, n * W * sizeof(uint32_t), (void **)&groups, &pooled);
+    hipError_t e = stream_scratch(s, n * W * sizeof(uint32_t), (void **)&groups);
     if (e != hipSuccess) return e;
     // (128 threads per group measured against 256 -- GM receive 72.5 -> 63% -- and a wave per group, four to a
     // workgroup -- 72.5 -> 62.4%)
@@ -6111,11 +6100,9 @@ static hipError_t launch_sum_copy_groups(const Src &src, size_t n, uint32_t *out
     if (e == hipSuccess) {
         uint32_t G = 1;
         while (G < W && G < 64u) G <<= 1;
-        hipLaunchKernelGGL(sum_group_join_kernel<Src>, dim3((unsigned)((n * G + 255) / 256)), dim3(256), 0, s, src, n, W,
-                           G, groups, out);
-        e = hipGetLastError();
+        e = launch_per_item(sum_group_join_kernel<Src>, n * G, s, src, n, W, G, groups, out);
     }
-    return scratch_done(s, groups, pooled, e);
+    return e;
 }
 
 // SUM message copies of fragments of R rows: the row groups to run (1: sum_copy_row_kernel's row items).
@@ -6177,11 +6164,10 @@ hipError_t launch_bcopy_desc(const lampi_copy_desc *d, size_t n, uint32_t *out, 
         const size_t F = kRowBytes / contig, nrow = n / F;
         if (row4k_rows(nrow) && nrow * F <= 0xFFFFFFFFull) {
             uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
-            bool pooled = false;
-            hipError_t e = stream_scratch(s, (nrow * F + 1) * sizeof(uint32_t), (void **)&list, &pooled);
+            hipError_t e = stream_scratch(s, (nrow * F + 1) * sizeof(uint32_t), (void **)&list);
             if (e != hipSuccess) return e;
             e = pair_counters(s, &left, &next_left);
-            if (e != hipSuccess) return scratch_done(s, list, pooled, e);
+            if (e != hipSuccess) return e;
             with_row4k_lanes(contig, [&](auto kG) {
                 hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0,
                                    s, d, img, out, list, left);
@@ -6193,7 +6179,6 @@ hipError_t launch_bcopy_desc(const lampi_copy_desc *d, size_t n, uint32_t *out, 
                 e = hipGetLastError();
             }
             if (e != hipSuccess) reset_pair_counters(s);
-            e = scratch_done(s, list, pooled, e);
             if (e != hipSuccess) return e;
             const size_t done = nrow * F;
             return done >= n ? hipSuccess : launch_bcopy_desc(d + done, n - done, out + done, mode, img, s, 1u);
@@ -6213,9 +6198,7 @@ __global__ void __launch_bounds__(256) zero_verdicts_kernel(uint32_t *__restrict
 // ... for n fragments
 static hipError_t zero_verdicts(uint32_t *mask, size_t n, uint32_t *nbad, hipStream_t s) {
     const size_t nwords = (n + 31) / 32;
-    hipLaunchKernelGGL(zero_verdicts_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, mask, nwords,
-                       nbad);
-    return hipGetLastError();
+    return launch_per_item(zero_verdicts_kernel, nwords, s, mask, nwords, nbad);
 }
 
 hipError_t launch_copy_to_app(const lampi_recv_desc *d, size_t n, const uint8_t *expected, size_t exp_stride,
@@ -6259,9 +6242,7 @@ __global__ void __launch_bounds__(256) zero_verdicts2_kernel(uint32_t *__restric
 }
 static hipError_t zero_verdicts2(uint32_t *hmask, uint32_t *dmask, size_t n, uint32_t *nbad, hipStream_t s) {
     const size_t nwords = (n + 31) / 32;
-    hipLaunchKernelGGL(zero_verdicts2_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, s, hmask, dmask,
-                       nwords, nbad);
-    return hipGetLastError();
+    return launch_per_item(zero_verdicts2_kernel, nwords, s, hmask, dmask, nwords, nbad);
 }
 
 // The header tests as a pass of their own: one thread per header on a 4 KiB LDS copy of the slice tables (as
@@ -6485,18 +6466,16 @@ static hipError_t launch_recv_hdr(Src src, size_t n, uint32_t *csum, const uint3
                      : prepass == 2 ? !none || ring
                                     : prepass == 1 && !none && (groups || (crc && sh.pairs));
     RecvHdrRec *rec = nullptr;
-    bool pooled = false;
     if (pre) {
-        hipError_t e = stream_vals(s, 2 * n, (uint32_t **)&rec, &pooled);
+        hipError_t e = stream_vals(s, 2 * n, (uint32_t **)&rec);
         if (e != hipSuccess) return e;
         if constexpr (quadrics)
-            hipLaunchKernelGGL(qrecv_hdr_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.hdrs,
-                               src.hdr_stride, (uint32_t)n, mode, max_len, img, rec);
+            e = launch_per_item(qrecv_hdr_test_kernel, n, s, src.hdrs, src.hdr_stride, (uint32_t)n, mode, max_len, img,
+                                rec);
         else
-            hipLaunchKernelGGL(recv_hdr_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src.hdrs,
-                               src.hdr_stride, (uint32_t)n, src.kind, mode, max_len, img, rec);
-        e = hipGetLastError();
-        if (e != hipSuccess) return scratch_done(s, rec, pooled, e);
+            e = launch_per_item(recv_hdr_test_kernel, n, s, src.hdrs, src.hdr_stride, (uint32_t)n, src.kind, mode,
+                                max_len, img, rec);
+        if (e != hipSuccess) return e;
         src.rec = rec;
     }
     hipError_t e;
@@ -6507,7 +6486,7 @@ static hipError_t launch_recv_hdr(Src src, size_t n, uint32_t *csum, const uint3
     } else {
         e = launch_fused_copy(src, crc, n, img, csum, s, sh);
     }
-    return pre ? scratch_done(s, rec, pooled, e) : e;
+    return e;
 }
 
 static void fill_recv_hdr_base(RecvHdrBase &b, const uint8_t *hdrs, size_t hdr_stride, int kind, int mode,
@@ -6848,8 +6827,7 @@ static hipError_t launch_crc_light_copy(const uint8_t *base, size_t msg_len, siz
         return hipGetLastError();
     }
     uint32_t *rows = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_scratch(s, items * sizeof(uint32_t), (void **)&rows, &pooled);
+    hipError_t e = stream_scratch(s, items * sizeof(uint32_t), (void **)&rows);
     if (e != hipSuccess) return e;
     launch(rows);
     e = hipGetLastError();
@@ -6859,7 +6837,7 @@ static hipError_t launch_crc_light_copy(const uint8_t *base, size_t msg_len, siz
                            R, out);
         e = hipGetLastError();
     }
-    return scratch_done(s, rows, pooled, e);
+    return e;
 }
 
 // out[0, n) = 0 on s before row sums add into it: hipMemsetAsync, except while s is being captured.  A memset
@@ -6877,8 +6855,7 @@ static hipError_t zero_words(uint32_t *out, size_t n, hipStream_t s) {
     const hipError_t e = hipStreamIsCapturing(s, &cs);
     if (e != hipSuccess) return e;
     if (cs == hipStreamCaptureStatusNone) return hipMemsetAsync(out, 0, n * sizeof(uint32_t), s);
-    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n);
-    return hipGetLastError();
+    return launch_per_item(zero_words_kernel, n, s, out, n);
 }
 
 // sum_row4k_copy_kernel over the message's nrow whole 4 KiB rows (row4k_len(frag_len), row4k_rows(nrow))
@@ -6963,9 +6940,8 @@ hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len
 hipError_t launch_header_csum(const uint8_t *hdrs, size_t n, size_t stride, uint32_t crclen, uint32_t word_count,
                               int mode, const uint32_t *img, uint8_t *out, size_t out_stride, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(header_csum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs, (uint32_t)n, stride,
-                       crclen, word_count, mode, img, out, out_stride);
-    return hipGetLastError();
+    return launch_per_item(header_csum_kernel, n, s, hdrs, (uint32_t)n, stride, crclen, word_count, mode, img, out,
+                           out_stride);
 }
 
 hipError_t launch_header_check(const uint8_t *hdrs, size_t n, size_t stride, uint32_t hdr_bytes, uint32_t word_count,
@@ -6973,34 +6949,29 @@ hipError_t launch_header_check(const uint8_t *hdrs, size_t n, size_t stride, uin
                                hipStream_t s) {
     hipError_t e = hipMemsetAsync(nbad, 0, sizeof(uint32_t), s);
     if (e != hipSuccess || n == 0) return e;
-    hipLaunchKernelGGL(header_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs, (uint32_t)n,
-                       stride, hdr_bytes, word_count, csum_offset, mode, img, mask, nbad);
-    return hipGetLastError();
+    return launch_per_item(header_check_kernel, n, s, hdrs, (uint32_t)n, stride, hdr_bytes, word_count, csum_offset,
+                           mode, img, mask, nbad);
 }
 
 hipError_t launch_header_compare(const uint8_t *hdrs, size_t n, size_t stride, uint32_t crclen, uint32_t csum_offset,
                                  int mode, const uint32_t *img, uint32_t *mask, uint32_t *nbad, hipStream_t s) {
     hipError_t e = hipMemsetAsync(nbad, 0, sizeof(uint32_t), s);
     if (e != hipSuccess || n == 0) return e;
-    header_compare_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(hdrs, (uint32_t)n, stride, crclen,
-                                                                         csum_offset, mode, img, mask, nbad);
-    return hipGetLastError();
+    return launch_per_item(header_compare_kernel, n, s, hdrs, (uint32_t)n, stride, crclen, csum_offset, mode, img,
+                           mask, nbad);
 }
 
 hipError_t launch_check_data(const uint32_t *calc, const uint8_t *expected, size_t exp_stride, const uint8_t *lengths,
                              size_t len_stride, size_t n, uint32_t *mask, uint32_t *nbad, hipStream_t s) {
     hipError_t e = hipMemsetAsync(nbad, 0, sizeof(uint32_t), s);
     if (e != hipSuccess || n == 0) return e;
-    hipLaunchKernelGGL(check_data_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, calc, expected,
-                       exp_stride, lengths, len_stride, (uint32_t)n, mask, nbad);
-    return hipGetLastError();
+    return launch_per_item(check_data_kernel, n, s, calc, expected, exp_stride, lengths, len_stride, (uint32_t)n, mask,
+                           nbad);
 }
 
 hipError_t launch_scatter_u32(const uint32_t *vals, size_t n, uint8_t *dst, size_t stride, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(scatter_u32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, vals, (uint32_t)n, dst,
-                       stride);
-    return hipGetLastError();
+    return launch_per_item(scatter_u32_kernel, n, s, vals, (uint32_t)n, dst, stride);
 }
 
 // The send step over descriptors (lampi_send_pack_batch): launch_bcopy_desc's dispatch of CopySource on SendSource,
@@ -7022,8 +6993,7 @@ hipError_t launch_scatter_u32(const uint32_t *vals, size_t n, uint8_t *dst, size
 static hipError_t launch_qsend_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, size_t hdr_stride, int mode,
                                     const uint32_t *img, hipStream_t s, uint32_t rows_hint) {
     uint32_t *vals = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    hipError_t e = stream_vals(s, n, &vals);
     if (e != hipSuccess) return e;
     const QSendSource src{d, hdrs, hdr_stride};
     if (mode == LAMPI_CSUM_NONE) {
@@ -7035,13 +7005,10 @@ static hipError_t launch_qsend_pack(const lampi_copy_desc *d, size_t n, uint8_t 
         const LearnedShape sh = learn_shape(src, n, s, kShapeQSendPack, rows_hint, shape_opts(mode));
         e = launch_fused_copy(src, mode == LAMPI_CSUM_CRC32, n, img, vals, s, sh);
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(qsend_stamp_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs, hdr_stride,
-                           (uint32_t)n, (const uint32_t *)vals, d, SendFill{}, (const uint8_t *)nullptr, (size_t)0,
-                           (size_t)0, 0, mode, img);
-        e = hipGetLastError();
-    }
-    return scratch_done(s, vals, pooled, e);
+    if (e == hipSuccess)
+        e = launch_per_item(qsend_stamp_kernel<false>, n, s, hdrs, hdr_stride, (uint32_t)n, (const uint32_t *)vals, d,
+                            SendFill{}, (const uint8_t *)nullptr, (size_t)0, (size_t)0, 0, mode, img);
+    return e;
 }
 
 hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, size_t hdr_stride, int kind, int mode,
@@ -7056,17 +7023,13 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
     // batch(vals): a launch writing the n checksums to scratch; then the stamp
     auto two_launches = [&](auto &&batch) {
         uint32_t *vals = nullptr;
-        bool pooled = false;
-        hipError_t e = stream_vals(s, n, &vals, &pooled);
+        hipError_t e = stream_vals(s, n, &vals);
         if (e != hipSuccess) return e;
         e = batch(vals);
-        if (e == hipSuccess && !(mode == LAMPI_CSUM_NONE && kind == LAMPI_SEND_HDR_GM)) {
-            hipLaunchKernelGGL(send_stamp_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs,
-                               hdr_stride, (uint32_t)n, (const uint32_t *)vals, d, SendFill{}, (size_t)0, (size_t)0, kind,
-                               mode, img);
-            e = hipGetLastError();
-        }
-        return scratch_done(s, vals, pooled, e);
+        if (e == hipSuccess && !(mode == LAMPI_CSUM_NONE && kind == LAMPI_SEND_HDR_GM))
+            e = launch_per_item(send_stamp_kernel<false>, n, s, hdrs, hdr_stride, (uint32_t)n, (const uint32_t *)vals, d,
+                                SendFill{}, (size_t)0, (size_t)0, kind, mode, img);
+        return e;
     };
     if (fused == 0)
         return two_launches([&](uint32_t *vals) { return launch_bcopy_desc(d, n, vals, mode, img, s, rows_hint); });
@@ -7089,16 +7052,18 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
 // several of which have no single owner of a fragment (sum_copy_row_kernel's atomic row sums, the two-pass CRC
 // copies, the sum_row4k rows) -- with the checksums in pooled scratch, then one send_stamp_kernel<true> that writes
 // the headers.  Checksumming off: the SUM copy schedules, their sums unused (as lampi_msg_bcopy_strided).
-// The read-only checksums of a message's fragments (lampi_msg_csum's dispatch): the fastest kernels there are for
-// fragments that are not copied.
-static hipError_t msg_csum_readonly(const uint8_t *base, size_t msg_len, size_t frag_len, size_t n, uint32_t *out,
-                                    int mode, const uint32_t *img, int grid, hipStream_t s) {
+// The read-only checksums of a message's fragments (lampi_msg_csum, the host pipeline's chunks, the Quadrics
+// sender's fragments that are not copied): the regular kernel for whole-4-KiB-row fragments at a 16-byte-aligned
+// base, the piece streams otherwise.
+hipError_t launch_msg_csum(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
+                           int mode, const uint32_t *img, int grid, hipStream_t s) {
+    const size_t n = msg_len ? (msg_len + frag_len - 1) / frag_len : 1;
     if (mode == LAMPI_CSUM_SUM32) return launch_sum_msg(base, msg_len, frag_len, n, out, img, grid, s);
     const bool regular = msg_len != 0 && frag_len % kRowBytes == 0 && msg_len % frag_len == 0 &&
                          regular_msg_frag(frag_len, false) && ((uintptr_t)base & 15u) == 0 &&
                          !crc_light_msg(frag_len, msg_len);
-    if (regular) return launch_crc_regular(base, n, frag_len, kCrcInit, out, img, grid, s);
-    return launch_crc_msg(base, msg_len, frag_len, kCrcInit, n, out, img, grid, s);
+    if (regular) return launch_crc_regular(base, n, frag_len, partial, out, img, grid, s);
+    return launch_crc_msg(base, msg_len, frag_len, partial, n, out, img, grid, s);
 }
 
 // The Quadrics kind of the message form: the first launch leaves the fragments' checksums in vals, the stamp builds
@@ -7112,19 +7077,18 @@ static hipError_t launch_qmsg_send_pack(const uint8_t *base, size_t msg_len, siz
                                         size_t slot_stride, const SendFill &f, size_t n, int mode, const uint32_t *img,
                                         int grid, hipStream_t s) {
     uint32_t *vals = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    hipError_t e = stream_vals(s, n, &vals);
     if (e != hipSuccess) return e;
     const bool none = mode == LAMPI_CSUM_NONE, bare = slot_stride == kQHdrBytes && frag_len > kQInline;
     // checksumming off, fragments of 53 bytes .. one row that launch_msg_bcopy would give a workgroup each: the same
     // copy, the envelopes from its emit, one launch
     if (none && !bare && msg_len != 0 && frag_len > kQInline && frag_len < (size_t)kRowBytes && !row4k_len(frag_len)) {
         launch_sum_copy(QMsgEnvelopeSource{base, msg_len, frag_len, ring, slot_stride, f}, n, vals, s);
-        return scratch_done(s, vals, pooled, hipGetLastError());
+        return hipGetLastError();
     }
     if (msg_len != 0) {
         if (frag_len <= kQInline || bare) {
-            if (!none) e = msg_csum_readonly(base, msg_len, frag_len, n, vals, mode, img, grid, s);
+            if (!none) e = launch_msg_csum(base, msg_len, frag_len, kCrcInit, vals, mode, img, grid, s);
         } else {
             const size_t last = msg_len - (n - 1) * frag_len;
             const size_t nfull = last <= kQInline ? n - 1 : n;
@@ -7132,23 +7096,17 @@ static hipError_t launch_qmsg_send_pack(const uint8_t *base, size_t msg_len, siz
                 e = launch_msg_bcopy(base, std::min(msg_len, nfull * frag_len), frag_len, kCrcInit, ring + kQHdrBytes,
                                      slot_stride, nfull, vals, none ? LAMPI_CSUM_SUM32 : mode, img, s);
             if (e == hipSuccess && nfull < n && !none)
-                e = msg_csum_readonly(base + nfull * frag_len, last, last, 1, vals + nfull, mode, img, grid, s);
+                e = launch_msg_csum(base + nfull * frag_len, last, last, kCrcInit, vals + nfull, mode, img, grid, s);
         }
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(qsend_stamp_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ring, slot_stride,
-                           (uint32_t)n, (const uint32_t *)vals, (const lampi_copy_desc *)nullptr, f, base, msg_len,
-                           frag_len, bare ? 1 : 0, mode, img);
-        e = hipGetLastError();
-    }
-    return scratch_done(s, vals, pooled, e);
+    if (e == hipSuccess)
+        e = launch_per_item(qsend_stamp_kernel<true>, n, s, ring, slot_stride, (uint32_t)n, (const uint32_t *)vals,
+                            (const lampi_copy_desc *)nullptr, f, base, msg_len, frag_len, bare ? 1 : 0, mode, img);
+    return e;
 }
 
-hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
-                                size_t slot_stride, const lampi_send_hdr_fill &fill, size_t n, int kind, int mode,
-                                const uint32_t *img, hipStream_t s, int grid) {
-    if (n == 0) return hipSuccess;
-    if (!img) return hipErrorInvalidValue;
+// The kernels' copy of the caller's header template and per-fragment series (both message-form senders).
+static SendFill send_fill(const lampi_send_hdr_fill &fill) {
     SendFill f;
     static_assert(sizeof(f.tmpl) == sizeof(fill.tmpl), "header template");
     std::memcpy(f.tmpl, fill.tmpl, sizeof(f.tmpl));
@@ -7157,23 +7115,28 @@ hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag
     f.desc_ptr0 = fill.desc_ptr0;
     f.desc_ptr_stride = fill.desc_ptr_stride;
     f.seq_offset0 = fill.seq_offset0;
+    return f;
+}
+
+hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
+                                size_t slot_stride, const lampi_send_hdr_fill &fill, size_t n, int kind, int mode,
+                                const uint32_t *img, hipStream_t s, int grid) {
+    if (n == 0) return hipSuccess;
+    if (!img) return hipErrorInvalidValue;
+    const SendFill f = send_fill(fill);
     if (kind == LAMPI_SEND_HDR_QUADRICS)
         return launch_qmsg_send_pack(base, msg_len, frag_len, ring, slot_stride, f, n, mode, img, grid, s);
     uint32_t *vals = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    hipError_t e = stream_vals(s, n, &vals);
     if (e != hipSuccess) return e;
     const bool none = mode == LAMPI_CSUM_NONE;
     if (!(none && msg_len == 0))  // (nothing to copy, no checksum)
         e = launch_msg_bcopy(base, msg_len, frag_len, kCrcInit, ring + kSendHdrBytes, slot_stride, n, vals,
                              none ? LAMPI_CSUM_SUM32 : mode, img, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(send_stamp_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ring, slot_stride,
-                           (uint32_t)n, (const uint32_t *)vals, (const lampi_copy_desc *)nullptr, f, msg_len, frag_len,
-                           kind, mode, img);
-        e = hipGetLastError();
-    }
-    return scratch_done(s, vals, pooled, e);
+    if (e == hipSuccess)
+        e = launch_per_item(send_stamp_kernel<true>, n, s, ring, slot_stride, (uint32_t)n, (const uint32_t *)vals,
+                            (const lampi_copy_desc *)nullptr, f, msg_len, frag_len, kind, mode, img);
+    return e;
 }
 
 // ---- the typemap forms of both steps (lampi_tmap_send_pack / lampi_tmap_recv_unpack) -----------------------
@@ -7195,9 +7158,9 @@ hipError_t launch_chain(const lampi_copy_desc *d, size_t npieces, const uint32_t
     constexpr uint32_t kSmall = 256;  // pieces up to this many bytes: one thread each
     const bool sum = mode != LAMPI_CSUM_CRC32;
     if (npieces) {
-        if (sum)
-            hipLaunchKernelGGL(chain_phase_kernel, dim3((unsigned)((nfrags + 255) / 256)), dim3(256), 0, s, d, first,
-                               (uint32_t)nfrags, phase);
+        hipError_t e = hipSuccess;
+        if (sum) e = launch_per_item(chain_phase_kernel, nfrags, s, d, first, (uint32_t)nfrags, phase);
+        if (e != hipSuccess) return e;
         const uint32_t fpw = pick_fpw(npieces, 1);
         const PieceSource src{d, sum ? phase : nullptr, kSmall};
         if (sum)
@@ -7205,8 +7168,8 @@ hipError_t launch_chain(const lampi_copy_desc *d, size_t npieces, const uint32_t
                                fpw, vals);
         else
             launch_crc_rows_copy(src, npieces, 1, img, vals, s);
-        hipLaunchKernelGGL(chain_small_kernel, dim3((unsigned)((npieces + 255) / 256)), dim3(256), 0, s, d,
-                           (uint32_t)npieces, phase, kSmall, mode, img, vals);
+        e = launch_per_item(chain_small_kernel, npieces, s, d, (uint32_t)npieces, phase, kSmall, mode, img, vals);
+        if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(chain_fold_kernel, dim3((unsigned)((nfrags + kWaves - 1) / kWaves)), dim3(kBlock), 0, s, d, first,
                        (uint32_t)nfrags, vals, mode, img, out, v);

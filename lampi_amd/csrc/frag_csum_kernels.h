@@ -43,6 +43,10 @@ hipError_t launch_desc_per_wave(const lampi_frag_desc *d, size_t n, uint32_t *ou
                                 hipStream_t s);
 hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, size_t n,
                           uint32_t *out, const uint32_t *img, int grid, hipStream_t s);
+// Checksums of the fragments of a contiguous device-resident message, not copied (one for an empty message): the
+// regular kernel for whole-4-KiB-row fragments at a 16-byte-aligned base, the piece streams otherwise.
+hipError_t launch_msg_csum(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
+                           int mode, const uint32_t *img, int grid, hipStream_t s);
 // Regular batch: frag_len % 4096 == 0, base 16-byte aligned, n full fragments.
 hipError_t launch_crc_regular(const uint8_t *base, size_t n, size_t frag_len, uint32_t partial, uint32_t *out,
                               const uint32_t *img, int grid, hipStream_t s);

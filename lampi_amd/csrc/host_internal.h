@@ -11,12 +11,14 @@ namespace lampi {
 hipError_t current_device(int *dev);
 // The per-device table image (built once per process, uploaded once per device).
 hipError_t device_tables(int dev, const uint32_t **out);
-
-// Checksums of the fragments of a contiguous device-resident message (lampi_msg_csum's kernel
-// choice: the regular kernel for whole-4-KiB-row fragments at a 16-byte-aligned base, the piece
-// streams otherwise).  n = number of fragments, >= 1.
-hipError_t launch_msg_csum(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
-                           int mode, int dev, const uint32_t *img, hipStream_t s);
+// Both: what a device entry point asks for once its arguments have passed (tables false: the device alone, for
+// the entry points whose kernels read no table -- they must not start the upload).
+struct DeviceCall {
+    int dev;
+    const uint32_t *img;
+    hipError_t err;
+};
+DeviceCall device_call(bool tables = true);
 
 // Pinned host memory held by the library's own staging (all threads), for leak checks
 // (lampi_host_pinned_bytes).  Every hipHostMalloc of the host paths goes through these two.

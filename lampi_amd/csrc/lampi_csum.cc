@@ -66,16 +66,12 @@ hipError_t device_tables(int dev, const uint32_t **out) {
     return t.err;
 }
 
-hipError_t launch_msg_csum(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
-                           int mode, int dev, const uint32_t *img, hipStream_t s) {
-    const size_t n = msg_len ? (msg_len + frag_len - 1) / frag_len : 1;
-    const int grid = crc_grid(dev);
-    if (mode == LAMPI_CSUM_SUM32) return launch_sum_msg(base, msg_len, frag_len, n, out, img, grid, s);
-    const bool regular = msg_len != 0 && frag_len % kRowBytes == 0 && msg_len % frag_len == 0 &&
-                         regular_msg_frag(frag_len, false) && ((uintptr_t)base & 15u) == 0 &&
-                         !crc_light_msg(frag_len, msg_len);
-    if (regular) return launch_crc_regular(base, n, frag_len, partial, out, img, grid, s);
-    return launch_crc_msg(base, msg_len, frag_len, partial, n, out, img, grid, s);
+DeviceCall device_call(bool tables) {
+    int dev = 0;
+    const uint32_t *img = nullptr;
+    hipError_t e = current_device(&dev);
+    if (e == hipSuccess && tables) e = device_tables(dev, &img);
+    return {dev, img, e};
 }
 
 hipError_t pinned_alloc(void **p, size_t bytes, unsigned flags) {
@@ -106,6 +102,87 @@ bool hdr_kind_ok(int kind) {
 }
 // the data header of a kind: gmHeaderData / ibDataHdr_t 72 bytes, quadricsCtlHdr_t 128
 size_t data_hdr_bytes(int kind) { return kind == LAMPI_SEND_HDR_QUADRICS ? 128 : 72; }
+
+// ------------------------------------------------------------------ what the device entry points refuse
+
+constexpr int kRefused = (int)hipErrorInvalidValue;
+
+// mode (hint bits already taken out where they are accepted): a checksum, or -- the copying entry points --
+// checksumming off as well
+bool csum_mode_ok(int mode) { return mode == LAMPI_CSUM_CRC32 || mode == LAMPI_CSUM_SUM32; }
+bool copy_mode_ok(int mode) { return csum_mode_ok(mode) || mode == LAMPI_CSUM_NONE; }
+// counts travel to the kernels as 32-bit words
+bool count_ok(size_t n) { return n <= 0xFFFFFFFFull; }
+// 32-bit records read or written at p + i * stride (p may be null here: who needs it is the entry point's rule)
+bool words_ok(const void *p, size_t stride) { return !((uintptr_t)p & 3u) && !(stride & 3u); }
+// an array of a kind's headers, hdr_stride apart (hdr_bytes: 72 for the forms that take no Quadrics)
+bool hdrs_ok(const void *d_hdrs, size_t hdr_stride, size_t hdr_bytes) {
+    return words_ok(d_hdrs, hdr_stride) && hdr_stride >= hdr_bytes;
+}
+// a ring of header + payload slots, slot_stride apart
+bool ring_ok(const void *d_ring, size_t slot_stride, size_t hdr_bytes) {
+    return !((uintptr_t)d_ring & 7u) && !(slot_stride & 7u) && slot_stride >= hdr_bytes;
+}
+// the per-fragment outputs of a receive step
+bool recv_outs_ok(const int64_t *d_copied, const uint32_t *d_csum, const uint32_t *d_hdr_mask,
+                  const uint32_t *d_data_mask) {
+    return d_copied && d_csum && d_hdr_mask && d_data_mask;
+}
+// A strided output (d_out 4-byte aligned, out_stride a multiple of 4 and >= 4) is valid for n words.
+bool strided_ok(const void *d_out, size_t out_stride, size_t n) {
+    return d_out && words_ok(d_out, out_stride) && out_stride >= 4 && count_ok(n);
+}
+// What both typemap forms refuse: the mode's extra bits, Quadrics (its inline payloads are placed from a contiguous
+// message), a typemap that cannot be walked.  *total = count * packed_size (< 2^63).
+bool tmap_args_ok(const lampi_tmap *h_tmap, int hdr_kind, int mode, uint64_t *total) {
+    if (!copy_mode_ok(mode)) return false;
+    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return false;
+    if (!h_tmap || !h_tmap->d_pairs || h_tmap->num_pairs == 0 || h_tmap->packed_size == 0 || h_tmap->reserved != 0)
+        return false;
+    if (h_tmap->count > (((uint64_t)1 << 63) - 1) / h_tmap->packed_size) return false;
+    *total = h_tmap->count * h_tmap->packed_size;
+    return true;
+}
+// What both descriptor forms of the typemap steps refuse on the host (the records and the message table are device
+// memory: what they hold is tested there, tmap_kernels.h: tmap_record).
+bool tmap_batch_args_ok(size_t n, size_t nmsgs, uint32_t max_len, const void *d_hdrs, size_t hdr_stride, int hdr_kind,
+                        int mode) {
+    if (!copy_mode_ok(mode)) return false;
+    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return false;
+    if (!hdrs_ok(d_hdrs, hdr_stride, 72)) return false;
+    if (nmsgs == 0 || !count_ok(nmsgs) || !count_ok(n)) return false;
+    const size_t R = std::max<size_t>(1, ((size_t)max_len + 4095) / 4096);  // the frame's rows: a word of scratch each
+    return n <= SIZE_MAX / sizeof(uint32_t) / R;
+}
+
+// Runs batch(vals) -- a launch writing n checksum words to vals -- and puts word i at d_out + i*out_stride:
+// straight into d_out when out_stride is 4, otherwise into stream-ordered scratch and then one 4-byte scatter
+// (the send side's dataChecksum @64 of each 72-byte gmHeaderData record: d_out = hdrs + 64, out_stride = the
+// buffer size).  d_out == nullptr: the words are discarded (the copies with checksumming off).
+template <class F>
+int with_out(size_t n, void *d_out, size_t out_stride, hipStream_t s, F &&batch) {
+    if (d_out && out_stride == 4) return batch((uint32_t *)d_out);
+    uint32_t *vals = nullptr;
+    hipError_t e = hipMallocAsync((void **)&vals, std::max<size_t>(n, 1) * sizeof(uint32_t), s);
+    if (e != hipSuccess) return to_int(e);
+    int r = batch(vals);
+    if (r == 0 && d_out) r = to_int(launch_scatter_u32(vals, n, (uint8_t *)d_out, out_stride, s));
+    const hipError_t f = hipFreeAsync(vals, s);
+    return r != 0 ? r : to_int(f);
+}
+
+// Runs chain(vals, phase) with launch_chain's two arrays of npieces words, stream-ordered as with_out's (null for
+// a batch without pieces).
+template <class F>
+int with_chain_scratch(size_t npieces, hipStream_t s, F &&chain) {
+    if (!npieces) return chain(nullptr, nullptr);
+    uint32_t *scratch = nullptr;
+    const hipError_t e = hipMallocAsync((void **)&scratch, 2 * npieces * sizeof(uint32_t), s);
+    if (e != hipSuccess) return to_int(e);
+    const int r = chain(scratch, scratch + npieces);
+    const hipError_t f = hipFreeAsync(scratch, s);
+    return r != 0 ? r : to_int(f);
+}
 
 // ------------------------------------------------------------------ host-path context
 
@@ -536,10 +613,9 @@ unsigned long lampi_bcopy_csum(const void *src, void *dst, unsigned long copylen
 
 int lampi_frag_csum64_batch(const lampi_frag_desc *d_descs, size_t n, uint64_t *d_out, void *stream) {
     if (n == 0) return 0;
-    if (!d_descs || !d_out) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
+    if (!d_descs || !d_out) return kRefused;
+    const DeviceCall c = device_call(false);
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_sum64_desc(d_descs, n, d_out, false, (hipStream_t)stream));
 }
 
@@ -548,19 +624,15 @@ int lampi_frag_csum_batch(const lampi_frag_desc *d_descs, size_t n, uint32_t *d_
     // (0: no hint -- small batches then run as row groups; 1: the caller's one-row hint keeps the count split)
     const uint32_t rows_hint = LAMPI_CSUM_ROWS_HINT_OF(mode);
     mode &= ~(LAMPI_CSUM_BY_BYTES | LAMPI_CSUM_ROWS_HINT_MASK);
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32) return to_int(hipErrorInvalidValue);
+    if (!csum_mode_ok(mode)) return kRefused;
     if (n == 0) return 0;
-    if (!d_descs || !d_out) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
+    if (!d_descs || !d_out) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
     if (mode == LAMPI_CSUM_SUM32)
-        return to_int(launch_sum_desc(d_descs, n, d_out, img, crc_grid(dev), s, by_bytes, rows_hint));
-    return to_int(launch_crc_desc(d_descs, n, d_out, img, crc_grid(dev), s, by_bytes, rows_hint));
+        return to_int(launch_sum_desc(d_descs, n, d_out, c.img, crc_grid(c.dev), s, by_bytes, rows_hint));
+    return to_int(launch_crc_desc(d_descs, n, d_out, c.img, crc_grid(c.dev), s, by_bytes, rows_hint));
 }
 
 // Internal diagnostic (not in include/lampi_csum.h): the read-only CRC piece-stream kernel's timeline,
@@ -568,15 +640,11 @@ int lampi_frag_csum_batch(const lampi_frag_desc *d_descs, size_t n, uint32_t *d_
 // or a negative hipError_t.
 int lampi_diag_stream_timeline(const lampi_frag_desc *d_descs, size_t n, uint32_t *d_out, uint64_t *d_stamps,
                                void *stream) {
-    if (n == 0 || !d_descs || !d_out || !d_stamps) return -to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return -to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return -to_int(e);
+    if (n == 0 || !d_descs || !d_out || !d_stamps) return -kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return -to_int(c.err);
     uint32_t nwg = 0;
-    e = diag_stream_timeline(d_descs, n, d_out, img, d_stamps, (hipStream_t)stream, &nwg);
+    const hipError_t e = diag_stream_timeline(d_descs, n, d_out, c.img, d_stamps, (hipStream_t)stream, &nwg);
     return e != hipSuccess ? -to_int(e) : (int)nwg;
 }
 
@@ -584,15 +652,12 @@ int lampi_diag_stream_timeline(const lampi_frag_desc *d_descs, size_t n, uint32_
 // fragments at d_base (n even), 16 u64 per workgroup into d_stamps (tools/microbench/regular_timeline.py).  Returns
 // the workgroup count or a negative hipError_t.
 int lampi_diag_regular_timeline(const void *d_base, size_t n, uint32_t *d_out, uint64_t *d_stamps, void *stream) {
-    if (n == 0 || !d_base || !d_out || !d_stamps) return -to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return -to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return -to_int(e);
+    if (n == 0 || !d_base || !d_out || !d_stamps) return -kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return -to_int(c.err);
     uint32_t nwg = 0;
-    e = diag_regular_timeline((const uint8_t *)d_base, n, d_out, img, d_stamps, (hipStream_t)stream, &nwg);
+    const hipError_t e =
+        diag_regular_timeline((const uint8_t *)d_base, n, d_out, c.img, d_stamps, (hipStream_t)stream, &nwg);
     return e != hipSuccess ? -to_int(e) : (int)nwg;
 }
 
@@ -601,51 +666,19 @@ int lampi_diag_regular_timeline(const void *d_base, size_t n, uint32_t *d_out, u
 // (crc_rows_kernel / sum_rows_kernel) -- kept for bench.py's config C comparison and the parity tests only.
 int lampi_diag_frag_csum_batch_per_wave(const lampi_frag_desc *d_descs, size_t n, uint32_t *d_out, int mode,
                                         void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32) return to_int(hipErrorInvalidValue);
+    if (!csum_mode_ok(mode)) return kRefused;
     if (n == 0) return 0;
-    if (!d_descs || !d_out) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
-    return to_int(launch_desc_per_wave(d_descs, n, d_out, mode, img, (hipStream_t)stream));
+    if (!d_descs || !d_out) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
+    return to_int(launch_desc_per_wave(d_descs, n, d_out, mode, c.img, (hipStream_t)stream));
 }
-
-}  // extern "C"
-
-namespace {
-// A strided output (d_out 4-byte aligned, out_stride a multiple of 4 and >= 4) is valid for n words.
-bool strided_ok(const void *d_out, size_t out_stride, size_t n) {
-    return d_out && !((uintptr_t)d_out & 3u) && !(out_stride & 3u) && out_stride >= 4 && n <= 0xFFFFFFFFull;
-}
-
-// Runs batch(vals) -- a launch writing n checksum words to vals -- and puts word i at d_out + i*out_stride:
-// straight into d_out when out_stride is 4, otherwise into stream-ordered scratch and then one 4-byte scatter
-// (the send side's dataChecksum @64 of each 72-byte gmHeaderData record: d_out = hdrs + 64, out_stride = the
-// buffer size).  d_out == nullptr: the words are discarded (the copies with checksumming off).
-template <class F>
-int with_out(size_t n, void *d_out, size_t out_stride, hipStream_t s, F &&batch) {
-    if (d_out && out_stride == 4) return batch((uint32_t *)d_out);
-    uint32_t *vals = nullptr;
-    hipError_t e = hipMallocAsync((void **)&vals, std::max<size_t>(n, 1) * sizeof(uint32_t), s);
-    if (e != hipSuccess) return to_int(e);
-    int r = batch(vals);
-    if (r == 0 && d_out) r = to_int(launch_scatter_u32(vals, n, (uint8_t *)d_out, out_stride, s));
-    const hipError_t f = hipFreeAsync(vals, s);
-    return r != 0 ? r : to_int(f);
-}
-}  // namespace
-
-extern "C" {
 
 int lampi_frag_csum_batch_strided(const lampi_frag_desc *d_descs, size_t n, void *d_out, size_t out_stride, int mode,
                                   void *stream) {
-    const int base_mode = mode & ~(LAMPI_CSUM_BY_BYTES | LAMPI_CSUM_ROWS_HINT_MASK);
-    if (base_mode != LAMPI_CSUM_CRC32 && base_mode != LAMPI_CSUM_SUM32) return to_int(hipErrorInvalidValue);
+    if (!csum_mode_ok(mode & ~(LAMPI_CSUM_BY_BYTES | LAMPI_CSUM_ROWS_HINT_MASK))) return kRefused;
     if (n == 0) return 0;
-    if (!d_descs || !strided_ok(d_out, out_stride, n)) return to_int(hipErrorInvalidValue);
+    if (!d_descs || !strided_ok(d_out, out_stride, n)) return kRefused;
     return with_out(n, d_out, out_stride, (hipStream_t)stream,
                     [&](uint32_t *vals) { return lampi_frag_csum_batch(d_descs, n, vals, mode, stream); });
 }
@@ -654,21 +687,15 @@ int lampi_frag_bcopy_batch_strided(const lampi_copy_desc *d_descs, size_t n, voi
                                    void *stream) {
     const uint32_t rows_hint = std::max(1u, LAMPI_CSUM_ROWS_HINT_OF(mode));
     const int base_mode = mode & ~LAMPI_CSUM_ROWS_HINT_MASK;
-    if (base_mode != LAMPI_CSUM_CRC32 && base_mode != LAMPI_CSUM_SUM32 && base_mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(base_mode)) return kRefused;
     const bool none = base_mode == LAMPI_CSUM_NONE;  // (d_out unused: may be NULL)
     if (n == 0) return 0;
-    if (!d_descs || (!none && !strided_ok(d_out, out_stride, n)) || n > 0xFFFFFFFFull)
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;  // CRC: the tables
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    if (!d_descs || (!none && !strided_ok(d_out, out_stride, n)) || !count_ok(n)) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     hipStream_t s = (hipStream_t)stream;
     return with_out(n, none ? nullptr : d_out, out_stride, s, [&](uint32_t *vals) {
-        return to_int(launch_bcopy_desc(d_descs, n, vals, base_mode, img, s, rows_hint));
+        return to_int(launch_bcopy_desc(d_descs, n, vals, base_mode, c.img, s, rows_hint));
     });
 }
 
@@ -681,20 +708,15 @@ int lampi_copy_to_app_batch(const lampi_recv_desc *d_descs, size_t n, const void
                             void *stream) {
     const uint32_t rows_hint = std::max(1u, LAMPI_CSUM_ROWS_HINT_OF(mode));
     mode &= ~LAMPI_CSUM_ROWS_HINT_MASK;
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(mode)) return kRefused;
     const bool check = mode != LAMPI_CSUM_NONE;  // (checksumming off: no expected values read)
     if (!d_nbad || (n && (!d_descs || (check && !d_expected) || !d_copied || !d_csum || !d_mask)) ||
-        ((uintptr_t)d_expected & 3u) || (expected_stride & 3u) || n > 0xFFFFFFFFull)
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;  // CRC: the tables
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+        !words_ok(d_expected, expected_stride) || !count_ok(n))
+        return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_copy_to_app(d_descs, n, (const uint8_t *)d_expected, expected_stride, d_copied, d_csum, d_mask,
-                                     d_nbad, mode, img, (hipStream_t)stream, rows_hint));
+                                     d_nbad, mode, c.img, (hipStream_t)stream, rows_hint));
 }
 
 // The receive step in one call (ref src/path/gm/path.cc:364-393, src/path/ib/path.cc:652-680, then
@@ -705,87 +727,64 @@ int lampi_recv_unpack_batch(const lampi_recv_desc *d_descs, size_t n, const void
                             uint32_t *d_data_mask, uint32_t *d_nbad, int mode, void *stream) {
     const uint32_t rows_hint = std::max(1u, LAMPI_CSUM_ROWS_HINT_OF(mode));
     mode &= ~LAMPI_CSUM_ROWS_HINT_MASK;  // (LAMPI_CSUM_BY_BYTES stays in and is refused)
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
-    if (!hdr_kind_ok(hdr_kind)) return to_int(hipErrorInvalidValue);
-    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < data_hdr_bytes(hdr_kind))
-        return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(mode) || !hdr_kind_ok(hdr_kind)) return kRefused;
+    if (!hdrs_ok(d_hdrs, hdr_stride, data_hdr_bytes(hdr_kind))) return kRefused;
     // (checksumming off: no header is read -- except Quadrics', which hold the inline payloads)
     const bool check = mode != LAMPI_CSUM_NONE || hdr_kind == LAMPI_SEND_HDR_QUADRICS;
-    if (!d_nbad || n > 0xFFFFFFFFull ||
-        (n && (!d_descs || (check && !d_hdrs) || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask)))
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    if (!d_nbad || !count_ok(n) ||
+        (n && (!d_descs || (check && !d_hdrs) || !recv_outs_ok(d_copied, d_csum, d_hdr_mask, d_data_mask))))
+        return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_recv_unpack(d_descs, n, check ? (const uint8_t *)d_hdrs : nullptr, hdr_stride, hdr_kind,
-                                     d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode, img, (hipStream_t)stream,
-                                     rows_hint));
+                                     d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode, c.img,
+                                     (hipStream_t)stream, rows_hint));
 }
 
 // ... over a ring of header + payload slots, every field from the headers (MsgRecvSource, launch_msg_recv_unpack)
 int lampi_msg_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride, int hdr_kind, void *d_app,
                           size_t app_len, uint64_t seq_offset0, int64_t *d_copied, uint32_t *d_csum,
                           uint32_t *d_hdr_mask, uint32_t *d_data_mask, uint32_t *d_nbad, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);  // (no hint bits: the slot size says the shape)
-    if (!hdr_kind_ok(hdr_kind)) return to_int(hipErrorInvalidValue);
-    if (((uintptr_t)d_ring & 7u) || (slot_stride & 7u) || slot_stride < data_hdr_bytes(hdr_kind))
-        return to_int(hipErrorInvalidValue);
-    if (!d_nbad || nslots > 0xFFFFFFFFull || (app_len && !d_app) ||
-        (nslots && (!d_ring || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask)))
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    // (no hint bits: the slot size says the shape)
+    if (!copy_mode_ok(mode) || !hdr_kind_ok(hdr_kind)) return kRefused;
+    if (!ring_ok(d_ring, slot_stride, data_hdr_bytes(hdr_kind))) return kRefused;
+    if (!d_nbad || !count_ok(nslots) || (app_len && !d_app) ||
+        (nslots && (!d_ring || !recv_outs_ok(d_copied, d_csum, d_hdr_mask, d_data_mask))))
+        return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_msg_recv_unpack((const uint8_t *)d_ring, nslots, slot_stride, hdr_kind, (uint8_t *)d_app,
                                          app_len, seq_offset0, d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode,
-                                         img, (hipStream_t)stream));
+                                         c.img, (hipStream_t)stream));
 }
 
 int lampi_msg_csum(const void *d_msg, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *d_out, int mode,
                    void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32) return to_int(hipErrorInvalidValue);
-    if (frag_len == 0 || frag_len > 0xFFFFFFFFull || !d_out || (msg_len && !d_msg))
-        return to_int(hipErrorInvalidValue);
+    if (!csum_mode_ok(mode)) return kRefused;
+    if (frag_len == 0 || !count_ok(frag_len) || !d_out || (msg_len && !d_msg)) return kRefused;
     // a zero-length message is one empty fragment (the path layer still sends a header)
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
-    return to_int(launch_msg_csum((const uint8_t *)d_msg, msg_len, frag_len, partial, d_out, mode, dev, img,
-                                  (hipStream_t)stream));
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
+    return to_int(launch_msg_csum((const uint8_t *)d_msg, msg_len, frag_len, partial, d_out, mode, c.img,
+                                  crc_grid(c.dev), (hipStream_t)stream));
 }
 
 int lampi_msg_bcopy_strided(const void *d_msg, size_t msg_len, size_t frag_len, void *d_dst, size_t dst_stride,
                             uint32_t partial, void *d_out, size_t out_stride, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(mode)) return kRefused;
     const bool none = mode == LAMPI_CSUM_NONE;  // (d_out unused: may be NULL)
     const size_t n = frag_len && msg_len ? (msg_len + frag_len - 1) / frag_len : 1;
-    if (frag_len == 0 || frag_len > 0xFFFFFFFFull || dst_stride < frag_len || (!none && !strided_ok(d_out, out_stride, n)) ||
+    if (frag_len == 0 || !count_ok(frag_len) || dst_stride < frag_len || (!none && !strided_ok(d_out, out_stride, n)) ||
         (msg_len && (!d_msg || !d_dst)))
-        return to_int(hipErrorInvalidValue);
+        return kRefused;
     if (none && msg_len == 0) return 0;  // (nothing to copy, no checksum)
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;  // CRC: the tables
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     hipStream_t s = (hipStream_t)stream;
     // checksumming off: the SUM copy schedules (every byte copied is read once; the sums are discarded)
     return with_out(n, none ? nullptr : d_out, out_stride, s, [&](uint32_t *vals) {
         return to_int(launch_msg_bcopy((const uint8_t *)d_msg, msg_len, frag_len, partial, (uint8_t *)d_dst, dst_stride,
-                                       n, vals, none ? LAMPI_CSUM_SUM32 : mode, img, s));
+                                       n, vals, none ? LAMPI_CSUM_SUM32 : mode, c.img, s));
     });
 }
 
@@ -801,64 +800,39 @@ int lampi_send_pack_batch(const lampi_copy_desc *d_descs, size_t n, void *d_hdrs
                           int mode, void *stream) {
     const uint32_t rows_hint = std::max(1u, LAMPI_CSUM_ROWS_HINT_OF(mode));
     const int base_mode = mode & ~LAMPI_CSUM_ROWS_HINT_MASK;
-    if (base_mode != LAMPI_CSUM_CRC32 && base_mode != LAMPI_CSUM_SUM32 && base_mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
-    if (!hdr_kind_ok(hdr_kind)) return to_int(hipErrorInvalidValue);
-    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < data_hdr_bytes(hdr_kind))
-        return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(base_mode) || !hdr_kind_ok(hdr_kind)) return kRefused;
+    if (!hdrs_ok(d_hdrs, hdr_stride, data_hdr_bytes(hdr_kind))) return kRefused;
     // GM with checksumming off writes no header word (gm/sendFrag.cc:153-155, :219): the headers may be absent
     const bool no_hdrs = base_mode == LAMPI_CSUM_NONE && hdr_kind == LAMPI_SEND_HDR_GM;
     if (n == 0) return 0;
-    if (!d_descs || (!d_hdrs && !no_hdrs) || n > 0xFFFFFFFFull) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
-    return to_int(launch_send_pack(d_descs, n, (uint8_t *)d_hdrs, hdr_stride, hdr_kind, base_mode, img,
+    if (!d_descs || (!d_hdrs && !no_hdrs) || !count_ok(n)) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
+    return to_int(launch_send_pack(d_descs, n, (uint8_t *)d_hdrs, hdr_stride, hdr_kind, base_mode, c.img,
                                    (hipStream_t)stream, rows_hint));
 }
 
 int lampi_msg_send_pack(const void *d_msg, size_t msg_len, size_t frag_len, void *d_ring, size_t slot_stride,
                         const lampi_send_hdr_fill *h_fill, int hdr_kind, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
-    if (!hdr_kind_ok(hdr_kind)) return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(mode) || !hdr_kind_ok(hdr_kind)) return kRefused;
     const size_t hb = data_hdr_bytes(hdr_kind);
-    if (frag_len == 0 || frag_len > 0xFFFFFFFFull || !d_ring || !h_fill || ((uintptr_t)d_ring & 7u) ||
-        (slot_stride & 7u) || slot_stride < hb || (msg_len && !d_msg))
-        return to_int(hipErrorInvalidValue);
+    if (frag_len == 0 || !count_ok(frag_len) || !d_ring || !h_fill || !ring_ok(d_ring, slot_stride, hb) ||
+        (msg_len && !d_msg))
+        return kRefused;
     if (hdr_kind == LAMPI_SEND_HDR_QUADRICS) {
         // fragments of at most 52 bytes travel in the envelope; longer ones need room after it, or a bare envelope
         // queue (slot_stride == 128: checksummed, not copied)
-        if (frag_len > 52 && slot_stride != hb && slot_stride - hb < frag_len) return to_int(hipErrorInvalidValue);
+        if (frag_len > 52 && slot_stride != hb && slot_stride - hb < frag_len) return kRefused;
     } else if (slot_stride - hb < frag_len) {
-        return to_int(hipErrorInvalidValue);
+        return kRefused;
     }
     // a zero-length message is one empty fragment (the path layer still sends a header)
     const size_t n = msg_len ? (msg_len + frag_len - 1) / frag_len : 1;
-    if (n > 0xFFFFFFFFull) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    if (!count_ok(n)) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_msg_send_pack((const uint8_t *)d_msg, msg_len, frag_len, (uint8_t *)d_ring, slot_stride, *h_fill,
-                                       n, hdr_kind, mode, img, (hipStream_t)stream, crc_grid(dev)));
-}
-
-// What both typemap forms refuse: the mode's extra bits, Quadrics (its inline payloads are placed from a contiguous
-// message), a typemap that cannot be walked.  *total = count * packed_size (< 2^63).
-static bool tmap_args_ok(const lampi_tmap *h_tmap, int hdr_kind, int mode, uint64_t *total) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE) return false;
-    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return false;
-    if (!h_tmap || !h_tmap->d_pairs || h_tmap->num_pairs == 0 || h_tmap->packed_size == 0 || h_tmap->reserved != 0)
-        return false;
-    if (h_tmap->count > (((uint64_t)1 << 63) - 1) / h_tmap->packed_size) return false;
-    *total = h_tmap->count * h_tmap->packed_size;
-    return true;
+                                       n, hdr_kind, mode, c.img, (hipStream_t)stream, crc_grid(c.dev)));
 }
 
 // The send step through a typemap (ref src/path/gm/sendFrag.cc:157-217, src/path/ib/sendFrag.cc:140-203): no
@@ -867,21 +841,17 @@ int lampi_tmap_send_pack(const void *d_base, const lampi_tmap *h_tmap, uint64_t 
                          size_t frag_len, void *d_ring, size_t slot_stride, const lampi_send_hdr_fill *h_fill,
                          int hdr_kind, int mode, void *stream) {
     uint64_t total = 0;
-    if (!tmap_args_ok(h_tmap, hdr_kind, mode, &total)) return to_int(hipErrorInvalidValue);
-    if (pack_off > total || pack_len > total - pack_off) return to_int(hipErrorInvalidValue);
-    if (frag_len == 0 || frag_len > 0xFFFFFFFFull || !d_ring || !h_fill || ((uintptr_t)d_ring & 7u) ||
-        (slot_stride & 7u) || slot_stride < 72 || slot_stride - 72 < frag_len || (pack_len && !d_base))
-        return to_int(hipErrorInvalidValue);
+    if (!tmap_args_ok(h_tmap, hdr_kind, mode, &total)) return kRefused;
+    if (pack_off > total || pack_len > total - pack_off) return kRefused;
+    if (frag_len == 0 || !count_ok(frag_len) || !d_ring || !h_fill || !ring_ok(d_ring, slot_stride, 72) ||
+        slot_stride - 72 < frag_len || (pack_len && !d_base))
+        return kRefused;
     const uint64_t n = pack_len ? (pack_len - 1) / frag_len + 1 : 1;  // (an empty window: one empty fragment)
-    if (n > 0xFFFFFFFFull) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    if (!count_ok(n)) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_tmap_send_pack((const uint8_t *)d_base, *h_tmap, pack_off, pack_len, frag_len, (uint8_t *)d_ring,
-                                        slot_stride, *h_fill, (size_t)n, hdr_kind, mode, img, (hipStream_t)stream));
+                                        slot_stride, *h_fill, (size_t)n, hdr_kind, mode, c.img, (hipStream_t)stream));
 }
 
 // The receive step through a typemap (ref src/path/common/BaseDesc.cc:72-163, 326-340): lampi_msg_recv_unpack's
@@ -890,52 +860,32 @@ int lampi_tmap_recv_unpack(const void *d_ring, size_t nslots, size_t slot_stride
                            const lampi_tmap *h_tmap, uint64_t seq_offset0, int64_t *d_copied, uint32_t *d_csum,
                            uint32_t *d_hdr_mask, uint32_t *d_data_mask, uint32_t *d_nbad, int mode, void *stream) {
     uint64_t total = 0;
-    if (!tmap_args_ok(h_tmap, hdr_kind, mode, &total)) return to_int(hipErrorInvalidValue);
-    if (((uintptr_t)d_ring & 7u) || (slot_stride & 7u) || slot_stride < 72) return to_int(hipErrorInvalidValue);
-    if (!d_nbad || nslots > 0xFFFFFFFFull || (total && !d_base) ||
-        (nslots && (!d_ring || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask)))
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    if (!tmap_args_ok(h_tmap, hdr_kind, mode, &total)) return kRefused;
+    if (!ring_ok(d_ring, slot_stride, 72)) return kRefused;
+    if (!d_nbad || !count_ok(nslots) || (total && !d_base) ||
+        (nslots && (!d_ring || !recv_outs_ok(d_copied, d_csum, d_hdr_mask, d_data_mask))))
+        return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_tmap_recv_unpack((const uint8_t *)d_ring, nslots, slot_stride, hdr_kind, (uint8_t *)d_base,
                                           *h_tmap, seq_offset0, d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode,
-                                          img, (hipStream_t)stream));
-}
-
-// What both descriptor forms of the typemap steps refuse on the host (the records and the message table are device
-// memory: what they hold is tested there, tmap_kernels.h: tmap_record).
-static bool tmap_batch_args_ok(size_t n, size_t nmsgs, uint32_t max_len, const void *d_hdrs, size_t hdr_stride,
-                               int hdr_kind, int mode) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE) return false;
-    if (hdr_kind != LAMPI_SEND_HDR_GM && hdr_kind != LAMPI_SEND_HDR_IB) return false;
-    if (((uintptr_t)d_hdrs & 3u) || (hdr_stride & 3u) || hdr_stride < 72) return false;
-    if (nmsgs == 0 || nmsgs > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return false;
-    const size_t R = std::max<size_t>(1, ((size_t)max_len + 4095) / 4096);  // the frame's rows: a word of scratch each
-    return n <= SIZE_MAX / sizeof(uint32_t) / R;
+                                          c.img, (hipStream_t)stream));
 }
 
 // The typemap send step over fragment records (tmap_kernels.h: launch_tmap_send_pack_batch)
 int lampi_tmap_send_pack_batch(const lampi_tmap_frag *d_frags, size_t n, const lampi_tmap_msg *d_msgs, size_t nmsgs,
                                uint32_t max_len, void *d_hdrs, size_t hdr_stride, int hdr_kind, int mode,
                                void *stream) {
-    if (!tmap_batch_args_ok(n, nmsgs, max_len, d_hdrs, hdr_stride, hdr_kind, mode)) return to_int(hipErrorInvalidValue);
+    if (!tmap_batch_args_ok(n, nmsgs, max_len, d_hdrs, hdr_stride, hdr_kind, mode)) return kRefused;
     // GM with checksumming off writes no header word (gm/sendFrag.cc:153-155, :219): the headers may be absent
     const bool no_hdrs = mode == LAMPI_CSUM_NONE && hdr_kind == LAMPI_SEND_HDR_GM;
-    if (!d_hdrs && !no_hdrs) return to_int(hipErrorInvalidValue);
+    if (!d_hdrs && !no_hdrs) return kRefused;
     if (n == 0) return 0;
-    if (!d_frags || !d_msgs) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    if (!d_frags || !d_msgs) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_tmap_send_pack_batch(d_frags, n, d_msgs, nmsgs, max_len, (uint8_t *)d_hdrs, hdr_stride, hdr_kind,
-                                              mode, img, (hipStream_t)stream));
+                                              mode, c.img, (hipStream_t)stream));
 }
 
 // The typemap receive step over fragment records (tmap_kernels.h: launch_tmap_recv_unpack_batch)
@@ -943,53 +893,35 @@ int lampi_tmap_recv_unpack_batch(const lampi_tmap_frag *d_frags, size_t n, const
                                  uint32_t max_len, const void *d_hdrs, size_t hdr_stride, int hdr_kind,
                                  int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask, uint32_t *d_data_mask,
                                  uint32_t *d_nbad, int mode, void *stream) {
-    if (!tmap_batch_args_ok(n, nmsgs, max_len, d_hdrs, hdr_stride, hdr_kind, mode)) return to_int(hipErrorInvalidValue);
+    if (!tmap_batch_args_ok(n, nmsgs, max_len, d_hdrs, hdr_stride, hdr_kind, mode)) return kRefused;
     // (checksumming off: no header is read)
-    if (!d_hdrs && mode != LAMPI_CSUM_NONE) return to_int(hipErrorInvalidValue);
-    if (!d_nbad || !d_copied || !d_csum || !d_hdr_mask || !d_data_mask) return to_int(hipErrorInvalidValue);
-    if (n && (!d_frags || !d_msgs)) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    if (!d_hdrs && mode != LAMPI_CSUM_NONE) return kRefused;
+    if (!d_nbad || !recv_outs_ok(d_copied, d_csum, d_hdr_mask, d_data_mask)) return kRefused;
+    if (n && (!d_frags || !d_msgs)) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_tmap_recv_unpack_batch(d_frags, n, d_msgs, nmsgs, max_len, (const uint8_t *)d_hdrs, hdr_stride,
-                                                hdr_kind, d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode, img,
+                                                hdr_kind, d_copied, d_csum, d_hdr_mask, d_data_mask, d_nbad, mode, c.img,
                                                 (hipStream_t)stream));
 }
 
 int lampi_chain_csum_batch_strided(const lampi_copy_desc *d_pieces, size_t npieces, const uint32_t *d_first,
                                    size_t nfrags, void *d_out, size_t out_stride, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(mode)) return kRefused;
     const bool none = mode == LAMPI_CSUM_NONE;  // (d_out unused: may be NULL)
     if (nfrags == 0) return 0;
     if (!d_first || (!none && !strided_ok(d_out, out_stride, nfrags)) || (npieces && !d_pieces) ||
-        npieces > 0xFFFFFFFFull || nfrags > 0xFFFFFFFFull)
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+        !count_ok(npieces) || !count_ok(nfrags))
+        return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     hipStream_t s = (hipStream_t)stream;
-    uint32_t *scratch = nullptr;
-    if (npieces) {
-        e = hipMallocAsync((void **)&scratch, 2 * npieces * sizeof(uint32_t), s);
-        if (e != hipSuccess) return to_int(e);
-    }
     // (checksumming off: launch_chain copies and writes zeros, here into discarded scratch)
-    int r = with_out(nfrags, none ? nullptr : d_out, out_stride, s, [&](uint32_t *vals) {
-        return to_int(launch_chain(d_pieces, npieces, d_first, nfrags, vals, mode, img, scratch,
-                                   scratch ? scratch + npieces : nullptr, s));
+    return with_chain_scratch(npieces, s, [&](uint32_t *pvals, uint32_t *phase) {
+        return with_out(nfrags, none ? nullptr : d_out, out_stride, s, [&](uint32_t *vals) {
+            return to_int(launch_chain(d_pieces, npieces, d_first, nfrags, vals, mode, c.img, pvals, phase, s));
+        });
     });
-    if (scratch) {
-        const int f = to_int(hipFreeAsync(scratch, s));
-        if (r == 0) r = f;
-    }
-    return r;
 }
 
 int lampi_chain_csum_batch(const lampi_copy_desc *d_pieces, size_t npieces, const uint32_t *d_first, size_t nfrags,
@@ -1000,26 +932,16 @@ int lampi_chain_csum_batch(const lampi_copy_desc *d_pieces, size_t npieces, cons
 int lampi_chain_copy_to_app_batch(const lampi_copy_desc *d_pieces, size_t npieces, const uint32_t *d_first,
                                   size_t nfrags, const void *d_expected, size_t expected_stride, int64_t *d_copied,
                                   uint32_t *d_csum, uint32_t *d_mask, uint32_t *d_nbad, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(mode)) return kRefused;
     const bool check = mode != LAMPI_CSUM_NONE;
-    if (!d_nbad) return to_int(hipErrorInvalidValue);
+    if (!d_nbad) return kRefused;
     hipStream_t s = (hipStream_t)stream;
     if (nfrags == 0) return to_int(hipMemsetAsync(d_nbad, 0, sizeof(uint32_t), s));
     if (!d_first || !d_copied || !d_csum || !d_mask || (check && !d_expected) || (npieces && !d_pieces) ||
-        ((uintptr_t)d_expected & 3u) || (expected_stride & 3u) || npieces > 0xFFFFFFFFull || nfrags > 0xFFFFFFFFull)
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
-    uint32_t *scratch = nullptr;
-    if (npieces) {
-        e = hipMallocAsync((void **)&scratch, 2 * npieces * sizeof(uint32_t), s);
-        if (e != hipSuccess) return to_int(e);
-    }
+        !words_ok(d_expected, expected_stride) || !count_ok(npieces) || !count_ok(nfrags))
+        return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     ChainVerdict v;
     v.expected = (const uint8_t *)d_expected;
     v.exp_stride = expected_stride;
@@ -1027,102 +949,79 @@ int lampi_chain_copy_to_app_batch(const lampi_copy_desc *d_pieces, size_t npiece
     v.mask = d_mask;
     v.nbad = d_nbad;
     v.init = 1;  // nonContigCopyFunction's first call starts from CRC_INITIAL_REGISTER
-    e = launch_chain(d_pieces, npieces, d_first, nfrags, d_csum, mode, img, scratch,
-                     scratch ? scratch + npieces : nullptr, s, &v);
-    if (scratch) {
-        const hipError_t f = hipFreeAsync(scratch, s);
-        if (e == hipSuccess) e = f;
-    }
-    return to_int(e);
+    return with_chain_scratch(npieces, s, [&](uint32_t *pvals, uint32_t *phase) {
+        return to_int(launch_chain(d_pieces, npieces, d_first, nfrags, d_csum, mode, c.img, pvals, phase, s, &v));
+    });
 }
 
 int lampi_header_csum_batch_strided(const void *d_hdrs, size_t n, size_t stride, uint32_t crclen, uint32_t word_count,
                                     void *d_out, size_t out_stride, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32 && mode != LAMPI_CSUM_NONE)
-        return to_int(hipErrorInvalidValue);
+    if (!copy_mode_ok(mode)) return kRefused;
     if (mode == LAMPI_CSUM_NONE) return 0;  // no header checksum with checksumming off (gm/sendFrag.cc:219-225)
     if (n == 0) return 0;
-    if (!d_hdrs || !strided_ok(d_out, out_stride, n) || ((uintptr_t)d_hdrs & 3u) || (stride & 3u))
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
-    return to_int(launch_header_csum((const uint8_t *)d_hdrs, n, stride, crclen, word_count, mode, img,
+    if (!d_hdrs || !strided_ok(d_out, out_stride, n) || !words_ok(d_hdrs, stride)) return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
+    return to_int(launch_header_csum((const uint8_t *)d_hdrs, n, stride, crclen, word_count, mode, c.img,
                                      (uint8_t *)d_out, out_stride, (hipStream_t)stream));
 }
 
 int lampi_header_csum_batch(const void *d_hdrs, size_t n, size_t stride, uint32_t crclen, uint32_t word_count,
                             uint32_t *d_out, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32) return to_int(hipErrorInvalidValue);
+    if (!csum_mode_ok(mode)) return kRefused;
     return lampi_header_csum_batch_strided(d_hdrs, n, stride, crclen, word_count, d_out, sizeof(uint32_t), mode,
                                            stream);
 }
 
 int lampi_header_check_batch(const void *d_hdrs, size_t n, size_t stride, uint32_t hdr_bytes, uint32_t word_count,
                              uint32_t csum_offset, uint32_t *d_mask, uint32_t *d_nbad, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32) return to_int(hipErrorInvalidValue);
-    if (!d_nbad || (n && (!d_hdrs || !d_mask)) || ((uintptr_t)d_hdrs & 3u) || (stride & 3u) || (csum_offset & 3u) ||
-        n > 0xFFFFFFFFull)
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
+    if (!csum_mode_ok(mode)) return kRefused;
+    if (!d_nbad || (n && (!d_hdrs || !d_mask)) || !words_ok(d_hdrs, stride) || (csum_offset & 3u) || !count_ok(n))
+        return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_header_check((const uint8_t *)d_hdrs, n, stride, hdr_bytes, word_count, csum_offset, mode,
-                                      img, d_mask, d_nbad, (hipStream_t)stream));
+                                      c.img, d_mask, d_nbad, (hipStream_t)stream));
 }
 
 int lampi_header_compare_batch(const void *d_hdrs, size_t n, size_t stride, uint32_t crclen, uint32_t csum_offset,
                                uint32_t *d_mask, uint32_t *d_nbad, int mode, void *stream) {
-    if (mode != LAMPI_CSUM_CRC32 && mode != LAMPI_CSUM_SUM32) return to_int(hipErrorInvalidValue);
-    if (!d_nbad || (n && (!d_hdrs || !d_mask)) || ((uintptr_t)d_hdrs & 3u) || (stride & 3u) || (csum_offset & 3u) ||
-        n > 0xFFFFFFFFull)
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    const uint32_t *img = nullptr;
-    e = device_tables(dev, &img);
-    if (e != hipSuccess) return to_int(e);
-    return to_int(launch_header_compare((const uint8_t *)d_hdrs, n, stride, crclen, csum_offset, mode, img, d_mask,
+    if (!csum_mode_ok(mode)) return kRefused;
+    if (!d_nbad || (n && (!d_hdrs || !d_mask)) || !words_ok(d_hdrs, stride) || (csum_offset & 3u) || !count_ok(n))
+        return kRefused;
+    const DeviceCall c = device_call();
+    if (c.err != hipSuccess) return to_int(c.err);
+    return to_int(launch_header_compare((const uint8_t *)d_hdrs, n, stride, crclen, csum_offset, mode, c.img, d_mask,
                                         d_nbad, (hipStream_t)stream));
 }
 
 int lampi_check_data_batch(const uint32_t *d_calc, const void *d_expected, size_t expected_stride,
                            const void *d_lengths, size_t lengths_stride, size_t n, uint32_t *d_mask, uint32_t *d_nbad,
                            void *stream) {
-    if (!d_nbad || (n && (!d_calc || !d_expected || !d_mask)) || ((uintptr_t)d_expected & 3u) ||
-        (expected_stride & 3u) || ((uintptr_t)d_lengths & 3u) || (lengths_stride & 3u) || n > 0xFFFFFFFFull)
-        return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
+    if (!d_nbad || (n && (!d_calc || !d_expected || !d_mask)) || !words_ok(d_expected, expected_stride) ||
+        !words_ok(d_lengths, lengths_stride) || !count_ok(n))
+        return kRefused;
+    const DeviceCall c = device_call(false);
+    if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_check_data(d_calc, (const uint8_t *)d_expected, expected_stride, (const uint8_t *)d_lengths,
                                     lengths_stride, n, d_mask, d_nbad, (hipStream_t)stream));
 }
 
 int lampi_fill_stream(void *d_dst, size_t nbytes, uint64_t seed, uint64_t byte_off, void *stream) {
     if (nbytes == 0) return 0;
-    if (!d_dst) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    return to_int(launch_fill_stream((uint8_t *)d_dst, nbytes, seed, byte_off, crc_grid(dev), (hipStream_t)stream));
+    if (!d_dst) return kRefused;
+    const DeviceCall c = device_call(false);
+    if (c.err != hipSuccess) return to_int(c.err);
+    return to_int(launch_fill_stream((uint8_t *)d_dst, nbytes, seed, byte_off, crc_grid(c.dev), (hipStream_t)stream));
 }
 
 int lampi_fill_stream_frags(void *d_dst, size_t n, size_t frag_len, uint64_t seed, uint64_t k0, uint64_t kstep,
                             void *stream) {
     if (n == 0) return 0;
-    if (!d_dst || frag_len == 0 || frag_len % 8 != 0 || ((uintptr_t)d_dst & 7u)) return to_int(hipErrorInvalidValue);
-    int dev = 0;
-    hipError_t e = current_device(&dev);
-    if (e != hipSuccess) return to_int(e);
-    return to_int(launch_fill_frags((uint64_t *)d_dst, n, frag_len / 8, seed, k0, kstep, crc_grid(dev),
+    if (!d_dst || frag_len == 0 || frag_len % 8 != 0 || ((uintptr_t)d_dst & 7u)) return kRefused;
+    const DeviceCall c = device_call(false);
+    if (c.err != hipSuccess) return to_int(c.err);
+    return to_int(launch_fill_frags((uint64_t *)d_dst, n, frag_len / 8, seed, k0, kstep, crc_grid(c.dev),
                                     (hipStream_t)stream));
 }
 

@@ -74,11 +74,8 @@ unsigned long bcopy_csum(const void *source, void *destination, unsigned long co
 // the table image is per device and built on first use anyway; calling this builds it for the
 // calling thread's current device up front.  No GPU: abort, as every host entry point does.
 void ulm_initialize_crc_table() {
-    int dev = 0;
-    hipError_t e = lampi::current_device(&dev);
-    const uint32_t *img = nullptr;
-    if (e == hipSuccess) e = lampi::device_tables(dev, &img);
-    if (e != hipSuccess) lampi::die("ulm_initialize_crc_table", e);
+    const lampi::DeviceCall c = lampi::device_call();
+    if (c.err != hipSuccess) lampi::die("ulm_initialize_crc_table", c.err);
 }
 
 // ref MemFunctions.cc:1380-1393 (declared in src/util/Utility.h:45): a debugging fill of

@@ -526,11 +526,10 @@ template <bool kRecv, bool kDesc = false>
 hipError_t launch_tmap_rows(TmapJob J, size_t n, uint32_t *vals, int mode, hipStream_t s) {
     const bool none = mode == LAMPI_CSUM_NONE;
     uint32_t *rows = nullptr;
-    bool pooled = false;
     J.nitems = n * J.R;
     J.rows = vals;
     if (!none && J.R > 1u) {
-        const hipError_t e = stream_scratch(s, J.nitems * sizeof(uint32_t), (void **)&rows, &pooled);
+        const hipError_t e = stream_scratch(s, J.nitems * sizeof(uint32_t), (void **)&rows);
         if (e != hipSuccess) return e;
         J.rows = rows;
     }
@@ -554,7 +553,7 @@ hipError_t launch_tmap_rows(TmapJob J, size_t n, uint32_t *vals, int mode, hipSt
             hipLaunchKernelGGL(tmap_sum_join_kernel, grid, dim3(256), 0, s, rows, n, J.R, vals);
         e = hipGetLastError();
     }
-    return rows ? scratch_done(s, rows, pooled, e) : e;
+    return e;
 }
 
 // The descriptor form's stamp: send_stamp_kernel<false>'s route (the prefix read from the header, on the LDS
@@ -655,17 +654,9 @@ hipError_t launch_tmap_send_pack(const uint8_t *base, const lampi_tmap &tm, uint
                                  size_t n, int kind, int mode, const uint32_t *img, hipStream_t s) {
     if (n == 0) return hipSuccess;
     if (!img) return hipErrorInvalidValue;
-    SendFill f;
-    static_assert(sizeof(f.tmpl) == sizeof(fill.tmpl), "header template");
-    std::memcpy(f.tmpl, fill.tmpl, sizeof(f.tmpl));
-    f.frag_seq0 = fill.frag_seq0;
-    f.frag_seq_step = fill.frag_seq_step;
-    f.desc_ptr0 = fill.desc_ptr0;
-    f.desc_ptr_stride = fill.desc_ptr_stride;
-    f.seq_offset0 = fill.seq_offset0;
+    const SendFill f = send_fill(fill);
     uint32_t *vals = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    hipError_t e = stream_vals(s, n, &vals);
     if (e != hipSuccess) return e;
     if (!(mode == LAMPI_CSUM_NONE && pack_len == 0)) {  // (nothing to copy, no checksum)
         TmapJob J = tmap_job(tm, const_cast<uint8_t *>(base), ring, slot_stride, frag_len, img);
@@ -674,13 +665,10 @@ hipError_t launch_tmap_send_pack(const uint8_t *base, const lampi_tmap &tm, uint
         J.frag_len = (uint32_t)frag_len;
         e = launch_tmap_rows<false>(J, n, vals, mode, s);
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(send_stamp_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ring, slot_stride,
-                           (uint32_t)n, (const uint32_t *)vals, (const lampi_copy_desc *)nullptr, f, (size_t)pack_len,
-                           frag_len, kind, mode, img);
-        e = hipGetLastError();
-    }
-    return scratch_done(s, vals, pooled, e);
+    if (e == hipSuccess)
+        e = launch_per_item(send_stamp_kernel<true>, n, s, ring, slot_stride, (uint32_t)n, (const uint32_t *)vals,
+                            (const lampi_copy_desc *)nullptr, f, (size_t)pack_len, frag_len, kind, mode, img);
+    return e;
 }
 
 // The receive step through a typemap (lampi_tmap_recv_unpack): the verdicts zeroed, recv_hdr_test_kernel over the
@@ -695,29 +683,25 @@ hipError_t launch_tmap_recv_unpack(const uint8_t *ring, size_t nslots, size_t sl
     hipError_t e = zero_verdicts2(hmask, dmask, nslots, nbad, s);
     if (e != hipSuccess) return e;
     uint32_t *buf = nullptr;  // the records (two words a slot), then the fragments' values
-    bool pooled = false;
-    e = stream_vals(s, 3 * nslots, &buf, &pooled);
+    e = stream_vals(s, 3 * nslots, &buf);
     if (e != hipSuccess) return e;
     RecvHdrRec *rec = (RecvHdrRec *)buf;
     uint32_t *vals = buf + 2 * nslots;
     const size_t room = std::min<size_t>(slot_stride - kSendHdrBytes, 0xFFFFFFFEull);
-    hipLaunchKernelGGL(recv_hdr_test_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s, ring, slot_stride,
-                       (uint32_t)nslots, kind, mode, (uint32_t)room, img, rec);
-    e = hipGetLastError();
+    e = launch_per_item(recv_hdr_test_kernel, nslots, s, ring, slot_stride, (uint32_t)nslots, kind, mode, (uint32_t)room,
+                        img, rec);
     if (e == hipSuccess) {
         TmapJob J = tmap_job(tm, base, const_cast<uint8_t *>(ring), slot_stride, room, img);
         J.rec = rec;
         J.seq0 = seq0;
         J.app_len = tm.count * tm.packed_size;
         e = launch_tmap_rows<true>(J, nslots, vals, mode, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(tmap_recv_verdict_kernel, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s, ring,
-                               slot_stride, (uint32_t)nslots, (const RecvHdrRec *)rec, (const uint32_t *)vals, seq0,
-                               J.app_len, mode, copied, csum, hmask, dmask, nbad);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess)
+            e = launch_per_item(tmap_recv_verdict_kernel, nslots, s, ring, slot_stride, (uint32_t)nslots,
+                                (const RecvHdrRec *)rec, (const uint32_t *)vals, seq0, J.app_len, mode, copied, csum,
+                                hmask, dmask, nbad);
     }
-    return scratch_done(s, buf, pooled, e);
+    return e;
 }
 
 // The send step over fragment records (lampi_tmap_send_pack_batch): the rows of every record gather its window
@@ -729,16 +713,13 @@ hipError_t launch_tmap_send_pack_batch(const lampi_tmap_frag *frags, size_t n, c
     if (n == 0) return hipSuccess;
     if (!img) return hipErrorInvalidValue;
     uint32_t *vals = nullptr;
-    bool pooled = false;
-    hipError_t e = stream_vals(s, n, &vals, &pooled);
+    hipError_t e = stream_vals(s, n, &vals);
     if (e != hipSuccess) return e;
     e = launch_tmap_rows<false, true>(tmap_batch_job(frags, msgs, nmsgs, max_len, img), n, vals, mode, s);
-    if (e == hipSuccess && !(mode == LAMPI_CSUM_NONE && kind == LAMPI_SEND_HDR_GM)) {
-        hipLaunchKernelGGL(tmap_send_stamp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs, hdr_stride,
-                           (uint32_t)n, (const uint32_t *)vals, frags, msgs, (uint32_t)nmsgs, max_len, kind, mode, img);
-        e = hipGetLastError();
-    }
-    return scratch_done(s, vals, pooled, e);
+    if (e == hipSuccess && !(mode == LAMPI_CSUM_NONE && kind == LAMPI_SEND_HDR_GM))
+        e = launch_per_item(tmap_send_stamp_kernel, n, s, hdrs, hdr_stride, (uint32_t)n, (const uint32_t *)vals, frags,
+                            msgs, (uint32_t)nmsgs, max_len, kind, mode, img);
+    return e;
 }
 
 // The receive step over fragment records (lampi_tmap_recv_unpack_batch): the verdicts zeroed, recv_hdr_test_kernel
@@ -753,27 +734,21 @@ hipError_t launch_tmap_recv_unpack_batch(const lampi_tmap_frag *frags, size_t n,
     hipError_t e = zero_verdicts2(hmask, dmask, n, nbad, s);
     if (e != hipSuccess) return e;
     uint32_t *buf = nullptr;  // the records (two words a fragment), then the fragments' values
-    bool pooled = false;
-    e = stream_vals(s, 3 * n, &buf, &pooled);
+    e = stream_vals(s, 3 * n, &buf);
     if (e != hipSuccess) return e;
     const bool none = mode == LAMPI_CSUM_NONE;
     RecvHdrRec *rec = none ? nullptr : (RecvHdrRec *)buf;
     uint32_t *vals = buf + 2 * n;
-    if (!none) {
-        hipLaunchKernelGGL(recv_hdr_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, hdrs, hdr_stride,
-                           (uint32_t)n, kind, mode, 0xFFFFFFFFu, img, rec);
-        e = hipGetLastError();
-    }
+    if (!none)
+        e = launch_per_item(recv_hdr_test_kernel, n, s, hdrs, hdr_stride, (uint32_t)n, kind, mode, 0xFFFFFFFFu, img,
+                            rec);
     if (e == hipSuccess) {
         TmapJob J = tmap_batch_job(frags, msgs, nmsgs, max_len, img);
         J.rec = rec;
         e = launch_tmap_rows<true, true>(J, n, vals, mode, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(tmap_batch_verdict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, frags,
-                               (uint32_t)n, msgs, (uint32_t)nmsgs, max_len, (const RecvHdrRec *)rec,
-                               (const uint32_t *)vals, mode, copied, csum, hmask, dmask, nbad);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess)
+            e = launch_per_item(tmap_batch_verdict_kernel, n, s, frags, (uint32_t)n, msgs, (uint32_t)nmsgs, max_len,
+                                (const RecvHdrRec *)rec, (const uint32_t *)vals, mode, copied, csum, hmask, dmask, nbad);
     }
-    return scratch_done(s, buf, pooled, e);
+    return e;
 }
