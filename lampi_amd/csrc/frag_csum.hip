@@ -52,28 +52,11 @@
 #include "crc_tables.h"
 #include "frag_csum_kernels.h"
 
-// A/B knobs (tools/ab/*.sh): the schedule switches measured against each other are read from the environment
-// only in the A/B build of the library (make AB=1: liblampi_csum_ab.so, -DLAMPI_AB_KNOBS=1, loaded by the A/B
-// scripts through LAMPI_CSUM_LIB).  The default library compiles each to its measured default and reads only
-// the documented switches (LAMPI_CSUM_NO_SHAPES here, LAMPI_HOST_CHUNK_BYTES in host_msg.cc); the knob names
-// do not appear in it (tests/test_abi.py).
-#if LAMPI_AB_KNOBS
-#define LAMPI_AB_ENV(name) std::getenv(name)
-#else
-#define LAMPI_AB_ENV(name) (static_cast<const char *>(nullptr))
-#endif
+// The schedule constants below are measured verdicts (the comment at each, profiles/, DESIGN.md's table of the
+// retired A/B knobs).  The library reads only the documented switches from the environment
+// (LAMPI_CSUM_NO_SHAPES here, LAMPI_HOST_CHUNK_BYTES in host_msg.cc; tests/test_abi.py).
 
 namespace lampi {
-
-// A knob's value from the string LAMPI_AB_ENV gave for it (null: the measured default).  Each reader keeps the
-// macro with the literal name at its own site: that is what keeps the name out of the default library.
-static bool knob_on(const char *e) { return !(e && e[0] == '0'); }  // on unless "0"
-static uint32_t knob_u32(const char *e, uint32_t dflt) { return e ? (uint32_t)std::atoi(e) : dflt; }
-static size_t knob_size(const char *e, size_t dflt) { return e ? (size_t)std::atoll(e) : dflt; }
-// waves per workgroup: "16", "8" or "4"
-static int knob_waves(const char *e, int dflt) {
-    return !e ? dflt : e[0] == '1' ? 16 : e[0] == '8' ? 8 : e[0] == '4' ? 4 : dflt;
-}
 
 // per-stream device scratch (defined with the launchers)
 static hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out);
@@ -3384,23 +3367,11 @@ __global__ void __launch_bounds__(256) crc_light_group_join_kernel(const Src src
 // and the 4 KiB descriptor lines unchanged (60.6-60.9%, 80.9%: the empty launch costs nothing visible in-stream).
 constexpr unsigned kLeftoverWgs = 256;
 
-// The table-light kernels come in workgroups of 16, 8 and 4 waves (the A/B knobs LAMPI_PAIR_WAVES and
-// LAMPI_LIGHT_WAVES choose): fn(std::integral_constant<int, kWv>) for the one asked for.
-template <class Fn>
-static void with_waves(int waves, Fn &&fn) {
-    if (waves == 16)
-        fn(std::integral_constant<int, 16>{});
-    else if (waves == 8)
-        fn(std::integral_constant<int, 8>{});
-    else
-        fn(std::integral_constant<int, 4>{});
-}
-
 template <class Src>
 static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uint32_t *img, uint32_t *out,
                                              hipStream_t s, uint32_t *shape_nhalf) {
     uint32_t *left = nullptr, *next_left = nullptr, *list = nullptr;
-    static const int kWv = knob_waves(LAMPI_AB_ENV("LAMPI_PAIR_WAVES"), 8);
+    constexpr int kWv = 8;  // waves per workgroup of the pair kernel
     const size_t nwg = (n + 2 * kWv - 1) / (2 * kWv);
     // (one entry per wave at most: a batch whose shape changed since the census leaves every wave)
     hipError_t e = stream_scratch(s, nwg * kWv * sizeof(uint32_t), (void **)&list);
@@ -3408,11 +3379,8 @@ static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uin
     // the counter pair is taken only now: a failure before this point leaves it untouched
     e = pair_counters(s, &left, &next_left);
     if (e != hipSuccess) return e;
-    with_waves(kWv, [&](auto wv) {
-        constexpr int kW = decltype(wv)::value;
-        hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, kW>), dim3((unsigned)nwg), dim3(64 * kW), 0, s, src, n, img,
-                           out, left, list);
-    });
+    hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, kWv>), dim3((unsigned)nwg), dim3(64 * kWv), 0, s, src, n, img,
+                       out, left, list);
     e = hipGetLastError();
     if (e == hipSuccess) {
         hipLaunchKernelGGL(crc_light_pair_leftover_kernel<Src>, dim3(kLeftoverWgs), dim3(256), 0, s, src, n, img, out,
@@ -3428,11 +3396,7 @@ static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uin
 // Eight (the same LDS, twice the waves per CU) lost 3-7 points on the copies and the read-only walk and was
 // box-dependent on the receive step (profiles/r04/light_waves_ab.txt, recv_waves_ab.txt); with the
 // single-row step (95 VGPRs) it lost there too: GM receive 72.2 against 69.0% (profiles/r04/last_row_ab.txt).
-// A/B knob LAMPI_LIGHT_WAVES = 4, 8, 16.
-static int light_waves() {
-    static const int w = knob_waves(LAMPI_AB_ENV("LAMPI_LIGHT_WAVES"), 4);
-    return w;
-}
+constexpr int kLightWaves = 4;
 
 // W: row groups per fragment (1: one wave walks all the fragment's rows)
 // the row groups a light launch runs with for a hint of W
@@ -3447,11 +3411,9 @@ static hipError_t launch_crc_light_frag_copy(const Src &src, size_t n, const uin
                                              hipStream_t s, uint32_t W = 1) {
     W = light_groups(n, W);
     auto launch = [&](size_t items, uint32_t *groups) {
-        with_waves(light_waves(), [&](auto wv) {
-            constexpr int kW = decltype(wv)::value;
-            hipLaunchKernelGGL((crc_light_frag_copy_kernel<Src, kW>), dim3((unsigned)((items + kW - 1) / kW)),
-                               dim3(64 * kW), 0, s, src, n, img, out, W, groups);
-        });
+        constexpr int kW = kLightWaves;
+        hipLaunchKernelGGL((crc_light_frag_copy_kernel<Src, kW>), dim3((unsigned)((items + kW - 1) / kW)),
+                           dim3(64 * kW), 0, s, src, n, img, out, W, groups);
     };
     if (W <= 1) {
         W = 1;
@@ -3646,6 +3608,7 @@ crc_regular_kernel(const uint8_t *__restrict__ base, uint32_t n, uint32_t fpw, s
     static_assert(kWv >= kWaves, "the table builders need 256 threads");
     static_assert(!kDesc || (kV <= 2 && !kCopy && !kSum), "descriptor batches: read-only CRC, kV = 1 or 2");
     static_assert(kSub == 64 || (kV == 2 && !kCopy && !kCoal && !kDesc), "packed rows: read-only, kV = 2");
+    static_assert(kSub == 64 || !kSum, "packed rows: CRC only (SUM runs on the sum_row4k kernels)");
     constexpr int kS = kCoal ? kRowBytes / 4 : 16;  // chunk stride of a lane
     __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsBytes / 4];
     const int lane = threadIdx.x & 63;
@@ -3672,7 +3635,7 @@ crc_regular_kernel(const uint8_t *__restrict__ base, uint32_t n, uint32_t fpw, s
     uint64_t pbad = 0u;
     const uint8_t *pbase = base;
     if constexpr (kSub < 64) {
-        if (dst != nullptr) {  // (SUM: the register is ignored; the pairs go to sum_pair_leftover_kernel)
+        if (dst != nullptr) {
             const lampi_frag_desc *pd = reinterpret_cast<const lampi_frag_desc *>(dst);
             const uint64_t a0 = uniform64(pd[0].addr);
             const uint32_t p0 = uniform(pd[0].partial);
@@ -3862,18 +3825,6 @@ crc_regular_kernel(const uint8_t *__restrict__ base, uint32_t n, uint32_t fpw, s
 #pragma unroll
                 for (int w = 0; w < 16; ++w) y += row_word(b.x[c], w);
                 C[c] = y;
-            }
-            if constexpr (kSub < 64) {  // packed rows: every group of kSub lanes is a fragment
-                uint32_t x[K];
-#pragma unroll
-                for (int c = 0; c < K; ++c) x[c] = group_reduce<kSub, true>(C[c]);
-                if ((lane & (kSub - 1)) == kSub - 1) {
-#pragma unroll
-                    for (int c = 0; c < K; ++c)
-                        if (K * t.i + c < nfr && !((pbad >> (K * t.i + c)) & 1u))
-                            out[(frag(t.i, c) * kV + t.r) * (64u / kSub) + lane / kSub] = x[c];
-                }
-                return;
             }
             if (kV > 1 || t.r + 1 == R) {
                 uint32_t x[K];
@@ -5095,11 +5046,7 @@ static void launch_crc_rows_copy(const Src &src, size_t n, uint32_t R, const uin
 // profiles/r02_bigfrag_ab.txt).
 constexpr uint32_t kCrcFpg = 96;
 static uint32_t frags_per_wg(size_t n, size_t frag_len = 0) {
-    static const uint32_t fpg_env = [] {  // (A/B knob LAMPI_STREAM_FPG: fragments per workgroup, <= 256)
-        const char *e = LAMPI_AB_ENV("LAMPI_STREAM_FPG");
-        return e ? (uint32_t)std::min(256, std::max(1, std::atoi(e))) : 0u;
-    }();
-    uint32_t fpg = fpg_env ? fpg_env : kCrcFpg;
+    uint32_t fpg = kCrcFpg;
     while (fpg > 3 && n / fpg < 256) fpg >>= 1;
     return spread_fpw(fpg, n, 1, frag_len);
 }
@@ -5505,11 +5452,7 @@ static LearnedShape learn_shape(const Src &src, size_t n, hipStream_t s, ShapeKi
     if (hipGetDevice(&dev) != hipSuccess) return ls;
     ScratchTable::Slot &slot = t_scratch.slots[{dev, s}];
     // this batch's record: the one of its descriptor array, else the least recently used one, reset
-    static const bool keyed = [] {  // (A/B knob LAMPI_SHAPES_UNKEYED=1: one record per kind, as in round 4)
-        const char *e = LAMPI_AB_ENV("LAMPI_SHAPES_UNKEYED");
-        return !(e && e[0] == '1');
-    }();
-    const void *key = keyed ? (const void *)src.d : nullptr;
+    const void *key = (const void *)src.d;
     ScratchTable::Slot::ShapeRec *sr = nullptr, *lru = &slot.shapes[0];
     for (auto &r : slot.shapes) {
         if (r.key == key && r.kind == kind) {
@@ -5677,13 +5620,7 @@ static hipError_t launch_crc_desc_whole(const lampi_frag_desc *d, size_t n, uint
     const size_t items = R == 1 ? n / 2 : n;  // pairs of 4 KiB fragments, or fragments
     const size_t span = R == 1 ? 2 * kRowBytes : (size_t)R * kRowBytes;
     if (items > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    // (A/B knob LAMPI_DESC_FPW: items per wave)
-    static const uint32_t fpw_env = knob_u32(LAMPI_AB_ENV("LAMPI_DESC_FPW"), 0u);
-    uint32_t fpw = pick_regular_fpw(items, span);
-    if (fpw_env) {
-        fpw = fpw_env;
-        while (fpw > 1 && (size_t)kWaves * fpw * 512 > items) fpw >>= 1;
-    }
+    const uint32_t fpw = pick_regular_fpw(items, span);
     if (fpw > (R == 1 ? 32u : 64u)) return hipErrorInvalidValue;  // (a wave's descriptors live in its 64 lanes)
     uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
     hipError_t e = stream_scratch(s, (items + 1) * sizeof(uint32_t), (void **)&list);
@@ -5716,16 +5653,15 @@ static hipError_t launch_crc_desc_whole(const lampi_frag_desc *d, size_t n, uint
 // whole 8 KiB items from d[0].addr, each wave checking its items' descriptors first; items holding anything else are
 // listed by fragment pairs for crc_light_pair_leftover_kernel; the last fragments (past the whole items) on the
 // count split.
-template <bool kSum, int kSub>
+template <int kSub>
 static hipError_t launch_packed_desc_k(const lampi_frag_desc *d, size_t nv, uint32_t *out, const uint32_t *img,
                                        hipStream_t s, uint32_t *list, uint32_t *left) {
     const uint32_t fpw = pick_regular_fpw(nv, 2 * kRowBytes);
-    hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, kSum, kWaves, 0, false, kSub>),
+    hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, false, kWaves, 0, false, kSub>),
                        grid_for(nv, fpw), dim3(kBlock), 0, s, (const uint8_t *)nullptr, (uint32_t)nv, fpw,
                        2 * kRowBytes, 0u, img, out, (uint8_t *)const_cast<lampi_frag_desc *>(d), (size_t)0, list, left);
     return hipGetLastError();
 }
-template <bool kSum>
 static hipError_t launch_desc_packed(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img,
                                      hipStream_t s, uint32_t L, size_t *done) {
     *done = 0;
@@ -5737,21 +5673,17 @@ static hipError_t launch_desc_packed(const lampi_frag_desc *d, size_t n, uint32_
     e = pair_counters(s, &left, &next_left);
     if (e != hipSuccess) return e;
     switch (L) {
-        case 64: e = launch_packed_desc_k<kSum, 1>(d, nv, out, img, s, list, left); break;
-        case 128: e = launch_packed_desc_k<kSum, 2>(d, nv, out, img, s, list, left); break;
-        case 256: e = launch_packed_desc_k<kSum, 4>(d, nv, out, img, s, list, left); break;
-        case 512: e = launch_packed_desc_k<kSum, 8>(d, nv, out, img, s, list, left); break;
-        case 1024: e = launch_packed_desc_k<kSum, 16>(d, nv, out, img, s, list, left); break;
-        default: e = launch_packed_desc_k<kSum, 32>(d, nv, out, img, s, list, left); break;
+        case 64: e = launch_packed_desc_k<1>(d, nv, out, img, s, list, left); break;
+        case 128: e = launch_packed_desc_k<2>(d, nv, out, img, s, list, left); break;
+        case 256: e = launch_packed_desc_k<4>(d, nv, out, img, s, list, left); break;
+        case 512: e = launch_packed_desc_k<8>(d, nv, out, img, s, list, left); break;
+        case 1024: e = launch_packed_desc_k<16>(d, nv, out, img, s, list, left); break;
+        default: e = launch_packed_desc_k<32>(d, nv, out, img, s, list, left); break;
     }
     if (e == hipSuccess) {
-        if constexpr (kSum)
-            hipLaunchKernelGGL(sum_pair_leftover_kernel, dim3(kLeftoverWgs), dim3(256), 0, s, d, nv * F, out,
-                               (const uint32_t *)left, next_left, (const uint32_t *)list);
-        else
-            hipLaunchKernelGGL(crc_light_pair_leftover_kernel<DescSource>, dim3(kLeftoverWgs), dim3(256), 0, s,
-                               DescSource{d}, nv * F, img, out, (const uint32_t *)left, next_left,
-                               (const uint32_t *)list, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(crc_light_pair_leftover_kernel<DescSource>, dim3(kLeftoverWgs), dim3(256), 0, s,
+                           DescSource{d}, nv * F, img, out, (const uint32_t *)left, next_left, (const uint32_t *)list,
+                           (uint32_t *)nullptr);
         e = hipGetLastError();
     }
     if (e != hipSuccess) reset_pair_counters(s);
@@ -5795,10 +5727,9 @@ static hipError_t launch_sum_desc_row4k(const lampi_frag_desc *d, size_t n, uint
 // small fragments pay the join launch, 200 x 4 KiB 8.3 -> 11.3 us (tools/microbench/small_batch.py,
 // profiles/r05/small_batch_ab.txt).  A shape learned per descriptor array would save that join but a stale
 // one-row shape would bring the 100x case back; the caller's LAMPI_CSUM_ROWS_HINT picks the best schedule
-// (one 64 MiB fragment: 168 us as groups, 55 us with the hint).  A/B knob LAMPI_SMALL_BATCH = the item
-// target (0: the count split).
+// (one 64 MiB fragment: 168 us as groups, 55 us with the hint).
 static uint32_t small_batch_groups(size_t n, hipStream_t s) {
-    static const size_t target = knob_size(LAMPI_AB_ENV("LAMPI_SMALL_BATCH"), (size_t)4096);
+    constexpr size_t target = 4096;  // items
     // graph captures keep the count split: the groups' scratch would be one more buffer held for the graph
     // (bench.py --latency: a replayed one-descriptor call 6.9 -> 32 us)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -5808,9 +5739,8 @@ static uint32_t small_batch_groups(size_t n, hipStream_t s) {
     return W;
 }
 
-hipError_t launch_crc_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img, int grid,
-                           hipStream_t s, bool plan, uint32_t rows_hint) {  // (defaults: frag_csum_kernels.h)
-    (void)grid;
+hipError_t launch_crc_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img, hipStream_t s,
+                           bool plan, uint32_t rows_hint) {  // (defaults: frag_csum_kernels.h)
     if (n == 0) return hipSuccess;
     if (plan && n <= kPlanMax) return launch_planned<false, kStreamWv, kStreamCap>(d, n, out, img, s);
     if (rows_hint == 0 && n < kShapeMin) {  // (1: the caller's pieces, count split)
@@ -5828,22 +5758,18 @@ hipError_t launch_crc_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, co
     const bool whole = sh.full_rows, small = sh.all_half;
     const uint32_t contig = sh.contig_len;
     // one contiguous run of equal 64 B .. 2 KiB fragments (a message as descriptors): packed rows, the rest after it
-    static const bool packed_desc = knob_on(LAMPI_AB_ENV("LAMPI_PACKED_DESC"));  // (A/B knob LAMPI_PACKED_DESC=0: off)
-    if (packed_desc && contig >= 64 && contig <= kRowBytes / 2 && (contig & (contig - 1)) == 0) {
+    if (contig >= 64 && contig <= kRowBytes / 2 && (contig & (contig - 1)) == 0) {
         size_t done = 0;
-        const hipError_t e = launch_desc_packed<false>(d, n, out, img, s, contig, &done);
+        const hipError_t e = launch_desc_packed(d, n, out, img, s, contig, &done);
         if (e != hipSuccess) return e;
-        if (done) return done >= n ? hipSuccess : launch_crc_desc(d + done, n - done, out + done, img, grid, s, false, 1u);
+        if (done) return done >= n ? hipSuccess : launch_crc_desc(d + done, n - done, out + done, img, s, false, 1u);
     }
-    // (A/B knob LAMPI_CRC_RO_PAIRS=0: read-only IB-sized batches on the piece streams)
-    static const bool ro_pairs = knob_on(LAMPI_AB_ENV("LAMPI_CRC_RO_PAIRS"));
-    if (sh.pairs && ro_pairs) return launch_crc_light_pair_copy(DescSource{d}, n, img, out, s, sh.nhalf_dev);
+    if (sh.pairs) return launch_crc_light_pair_copy(DescSource{d}, n, img, out, s, sh.nhalf_dev);
     // batches of equal whole-row fragments of 1-7 rows on the regular kernel (profiles/r05/crc_desc_pairs_ab.txt:
     // 4 KiB 76.4-77.8 -> 80.3-80.4%, 8 KiB 74.3 -> 77.8%, 16 KiB 74.7 -> 79.2%, 28 KiB 70.4 -> 75.4%; from 8 rows
-    // the table-light kernel stays ahead, 32 KiB 81 against 73%, 64 KiB 80 against 67%).  A/B knob
-    // LAMPI_CRC_DESC_REGULAR = the most rows taken (0: never).
-    static const uint32_t reg_desc = knob_u32(LAMPI_AB_ENV("LAMPI_CRC_DESC_REGULAR"), 7u);
-    if (whole && rows_hint >= 1u && rows_hint <= reg_desc && n >= 2 * kRegDescMinPairs)
+    // the table-light kernel stays ahead, 32 KiB 81 against 73%, 64 KiB 80 against 67%).
+    constexpr uint32_t kRegDescMaxRows = 7;
+    if (whole && rows_hint >= 1u && rows_hint <= kRegDescMaxRows && n >= 2 * kRegDescMinPairs)
         return launch_crc_desc_whole(d, n, out, img, s, rows_hint);
     if (given <= 1 && rows_hint < kShapeRows) rows_hint = given;  // (learned hints under 8 rows: as before)
     if (rows_hint >= kLightDescRows)  // one wave per kSegRows rows of a fragment, read-only
@@ -5919,13 +5845,11 @@ hipError_t launch_desc_per_wave(const lampi_frag_desc *d, size_t n, uint32_t *ou
     return hipGetLastError();
 }
 
-template <bool kSum>
 static hipError_t launch_packed(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
                                 const uint32_t *img, hipStream_t s, size_t *done);
 
 hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, size_t n,
-                          uint32_t *out, const uint32_t *img, int grid, hipStream_t s) {
-    (void)grid;
+                          uint32_t *out, const uint32_t *img, hipStream_t s) {
     if (n == 0) return hipSuccess;
     // the read-only table-light kernel (tools/microbench/msg_light.py, profiles/r03/msg_light_ab.txt):
     // fragments of 8-16 rows (GM's 65,456-byte payloads, 64 KiB) one wave each -- 4 GiB of 64 KiB
@@ -5936,22 +5860,15 @@ hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
     // non-whole-row 65,552-131,056 B on the framed regular kernel (removed) 71-76.5 -> 76-82%.
     // fragments of 64 B .. 2 KiB (powers of two) in packed rows of config B's kernel; the rest of the message
     // (its last fragments) through the schedules below
-    static const bool packed = knob_on(LAMPI_AB_ENV("LAMPI_PACKED"));  // (A/B knob LAMPI_PACKED=0: off)
-    if (packed) {
-        size_t done = 0;
-        const hipError_t e = launch_packed<false>(base, msg_len, frag_len, partial, out, img, s, &done);
-        if (e != hipSuccess || done == 0) {
-            if (e != hipSuccess) return e;
-        } else {
-            if (done >= n) return hipSuccess;
-            return launch_crc_msg(base + done * frag_len, msg_len - done * frag_len, frag_len, partial, n - done,
-                                  out + done, img, grid, s);
-        }
-    }
+    size_t done = 0;
+    const hipError_t e = launch_packed(base, msg_len, frag_len, partial, out, img, s, &done);
+    if (e != hipSuccess) return e;
+    if (done >= n) return hipSuccess;
+    if (done)
+        return launch_crc_msg(base + done * frag_len, msg_len - done * frag_len, frag_len, partial, n - done,
+                              out + done, img, s);
     const size_t R = (frag_len + kRowBytes - 1) / kRowBytes;
-    // (A/B knob LAMPI_CRC_RO_PAIRS=0, as launch_crc_desc)
-    static const bool ro_pairs = knob_on(LAMPI_AB_ENV("LAMPI_CRC_RO_PAIRS"));
-    if (ro_pairs && frag_len > 1024 && frag_len <= kRowBytes / 2 && (frag_len & 15u) != 0 && n >= kShapeMin &&
+    if (frag_len > 1024 && frag_len <= kRowBytes / 2 && (frag_len & 15u) != 0 && n >= kShapeMin &&
         pair_counters_ok(s))
         return launch_crc_light_pair_copy(MsgSource{base, msg_len, frag_len, partial}, n, img, out, s, nullptr);
     if (crc_light_msg(frag_len, msg_len))
@@ -6006,21 +5923,18 @@ static hipError_t launch_regular(const uint8_t *base, size_t n, size_t frag_len,
 // 2 KiB) at a 16-byte-aligned base on config B's schedule, 64 / kSub fragments per 4 KiB row, two rows per
 // chain item (kV = 2).  Takes the first *done fragments -- whole pairs of rows -- and leaves the rest (fewer
 // than 128 / kSub plus the message's last, possibly short, fragment) to the caller.
-template <bool kSum, int kSub>
+template <int kSub>
 static hipError_t launch_packed_k(const uint8_t *base, size_t nv, uint32_t partial, uint32_t *out, const uint32_t *img,
                                   hipStream_t s) {
-    // (A/B knob LAMPI_PACKED_FPW: items per wave)
-    static const uint32_t fpw_env = knob_u32(LAMPI_AB_ENV("LAMPI_PACKED_FPW"), 0u);
     // (config B's choice, 12 items per wave; 1 GiB of 1 KiB fragments: 16 items 71.4%, 8 70.6%, 6 70.5-70.9%, 4 66%;
     // a balanced grid of whole rounds of resident workgroups 68.6-71.1%, profiles/r06/packed_fpw.txt; a tapered grid
     // ending on 512-2,048 workgroups of 2-6 items 68-72%, profiles/r06/packed_taper.txt)
-    const uint32_t fpw = fpw_env ? fpw_env : pick_regular_fpw(nv, 2 * kRowBytes);
-    hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, kSum, kWaves, 0, false, kSub>),
+    const uint32_t fpw = pick_regular_fpw(nv, 2 * kRowBytes);
+    hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, false, kWaves, 0, false, kSub>),
                        grid_for(nv, fpw), dim3(kBlock), 0, s, base, (uint32_t)nv, fpw, 2 * kRowBytes, partial, img, out,
                        nullptr, (size_t)0);
     return hipGetLastError();
 }
-template <bool kSum>
 static hipError_t launch_packed(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
                                 const uint32_t *img, hipStream_t s, size_t *done) {
     *done = 0;
@@ -6030,12 +5944,12 @@ static hipError_t launch_packed(const uint8_t *base, size_t msg_len, size_t frag
     if (rows < kPackedMinRows || nv > 0xFFFFFFFFull) return hipSuccess;
     hipError_t e = hipErrorInvalidValue;
     switch (frag_len) {
-        case 64: e = launch_packed_k<kSum, 1>(base, nv, partial, out, img, s); break;
-        case 128: e = launch_packed_k<kSum, 2>(base, nv, partial, out, img, s); break;
-        case 256: e = launch_packed_k<kSum, 4>(base, nv, partial, out, img, s); break;
-        case 512: e = launch_packed_k<kSum, 8>(base, nv, partial, out, img, s); break;
-        case 1024: e = launch_packed_k<kSum, 16>(base, nv, partial, out, img, s); break;
-        case 2048: e = launch_packed_k<kSum, 32>(base, nv, partial, out, img, s); break;
+        case 64: e = launch_packed_k<1>(base, nv, partial, out, img, s); break;
+        case 128: e = launch_packed_k<2>(base, nv, partial, out, img, s); break;
+        case 256: e = launch_packed_k<4>(base, nv, partial, out, img, s); break;
+        case 512: e = launch_packed_k<8>(base, nv, partial, out, img, s); break;
+        case 1024: e = launch_packed_k<16>(base, nv, partial, out, img, s); break;
+        case 2048: e = launch_packed_k<32>(base, nv, partial, out, img, s); break;
         default: return hipSuccess;
     }
     if (e == hipSuccess) *done = nv * 2 * (kRowBytes / frag_len);
@@ -6043,8 +5957,7 @@ static hipError_t launch_packed(const uint8_t *base, size_t msg_len, size_t frag
 }
 
 hipError_t launch_crc_regular(const uint8_t *base, size_t n, size_t frag_len, uint32_t partial, uint32_t *out,
-                              const uint32_t *img, int grid, hipStream_t s) {
-    (void)grid;
+                              const uint32_t *img, hipStream_t s) {
     return launch_regular<false>(base, n, frag_len, partial, out, img, s);
 }
 
@@ -6111,16 +6024,11 @@ static hipError_t launch_sum_copy_groups(const Src &src, size_t n, uint32_t *out
 // word -- 256+ same-address atomics per fragment serialize at L2 -- for fragments of whole rows and for any
 // of >= 64 rows (profiles/r05/sum_msg_copy_ab.txt): 16 KiB 77.4 -> 79.9%, 128 KiB 76.7 -> 79.5%, 512 KiB
 // 65.7 -> 79.2%, 1 MiB 60.2 -> 78.7%, 4 MiB 49.0 -> 76.0%, 16 MiB 32.2 -> 67%.  GM's 65,456-byte fragments
-// (rows off the 16-byte grid) stay on the row items (77.2% against 71.3%).  A/B knobs LAMPI_SUM_CP_GRP_MIN
-// (fewest rows for fragments that are not whole rows, 0 = never groups), LAMPI_SUM_CP_GRP_ROWS (rows per group).
+// (rows off the 16-byte grid) stay on the row items (77.2% against 71.3%).
 static uint32_t sum_copy_groups(uint32_t R, bool whole_rows) {
-    static const uint32_t grp_min = knob_u32(LAMPI_AB_ENV("LAMPI_SUM_CP_GRP_MIN"), 64u);
-    static const uint32_t grp_rows = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_SUM_CP_GRP_ROWS");
-        return e ? (uint32_t)std::max(1, std::atoi(e)) : 1u;
-    }();
-    if (!grp_min || R < 2 || (!whole_rows && R < grp_min)) return 1u;
-    return (R + grp_rows - 1) / grp_rows;
+    constexpr uint32_t kGrpMinRows = 64;  // fewest rows for fragments that are not whole rows
+    if (R < 2 || (!whole_rows && R < kGrpMinRows)) return 1u;
+    return R;  // one row per group
 }
 
 // ---- the fused copies of descriptor batches: one dispatch ------------------------------------------------
@@ -6157,10 +6065,8 @@ hipError_t launch_bcopy_desc(const lampi_copy_desc *d, size_t n, uint32_t *out, 
     const uint32_t contig = sh.contig_len;
     // SUM copies of equal 64 B .. 1 KiB fragments: one short-lived workgroup per 4 KiB of them (sum_row4k_copy_desc_kernel),
     // the rest after them.  Same box, interleaved (profiles/r06/sum_row4k_cd_ab.txt), of read + write: 1 KiB 69.0 ->
-    // 77.3%, 256 B 23.7 -> 77.7%, 64 B 6.9 -> 63.0% (to + 8 / + 1 destinations 58-74%).  A/B knob
-    // LAMPI_SUM_ROW4K_COPY_DESC=0: off
-    static const bool row4k_cd = knob_on(LAMPI_AB_ENV("LAMPI_SUM_ROW4K_COPY_DESC"));
-    if (!crc && row4k_cd && given <= 1 && row4k_len(contig)) {
+    // 77.3%, 256 B 23.7 -> 77.7%, 64 B 6.9 -> 63.0% (to + 8 / + 1 destinations 58-74%).
+    if (!crc && given <= 1 && row4k_len(contig)) {
         const size_t F = kRowBytes / contig, nrow = n / F;
         if (row4k_rows(nrow) && nrow * F <= 0xFFFFFFFFull) {
             uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
@@ -6440,15 +6346,10 @@ __global__ void __launch_bounds__(256) qsend_stamp_kernel(uint8_t *hdrs, size_t 
 // workgroup and every join lane would repeat the test ahead of its first payload load (CRC: sixteen dependent table
 // rounds; measured behind the three calls, GM CRC 0.4725 against 0.4167 ms, GM SUM 0.3823 against 0.3746 ms): there
 // one recv_hdr_test_kernel runs first and get() reads its record from the stream's second pooled buffer (GM CRC
-// 0.4148, GM SUM 0.3639 ms).  A/B knob LAMPI_RECV_PREPASS: 0 = never, 2 = always (SUM waves and the ring form with
-// checksumming off too).
+// 0.4148, GM SUM 0.3639 ms).
 template <class Co, class Src>
 static hipError_t launch_recv_hdr(Src src, size_t n, uint32_t *csum, const uint32_t *img, hipStream_t s,
                                   const LearnedShape &sh, uint32_t max_len) {
-    static const int prepass = [] {
-        const char *e = LAMPI_AB_ENV("LAMPI_RECV_PREPASS");
-        return !e ? 1 : e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
-    }();
     const int mode = src.mode;
     const bool crc = mode == LAMPI_CSUM_CRC32, none = mode == LAMPI_CSUM_NONE;
     // row groups: the first launch zeroes the verdicts (zero_verdict_words), the join gives them; otherwise the
@@ -6459,12 +6360,9 @@ static hipError_t launch_recv_hdr(Src src, size_t n, uint32_t *csum, const uint3
         if (e != hipSuccess) return e;
     }
     // (checksumming off: the descriptor form reads no header; the ring form tests the length alone, in get())
-    const bool ring = max_len != 0xFFFFFFFFu;
     // (Quadrics sources: always with checksumming on, their get() has no header test of its own)
     constexpr bool quadrics = IsQuadricsRecv<Src>::value;
-    const bool pre = quadrics       ? !none
-                     : prepass == 2 ? !none || ring
-                                    : prepass == 1 && !none && (groups || (crc && sh.pairs));
+    const bool pre = !none && (quadrics || groups || (crc && sh.pairs));
     RecvHdrRec *rec = nullptr;
     if (pre) {
         hipError_t e = stream_vals(s, 2 * n, (uint32_t **)&rec);
@@ -6607,23 +6505,18 @@ hipError_t launch_sum64_finish(const uint64_t *vals, uint32_t nv, const uint8_t 
 //    per fragment above 8 rows loses wherever the grid needs more than one round of workgroups (512 KiB
 //    x 8,192 86.9 -> 75.4%, GM 86.7 -> 84.8%).
 //  - fragments over 256 rows were row segments before (2 MiB x 4,096 76.6 -> 84.8% as groups).
-// A/B knobs: LAMPI_SUM_RO_ONEWG = fewest fragments for one per workgroup (0: never), LAMPI_SUM_RO_WGS = the
-// workgroup target, LAMPI_SUM_RO_GROUPS=0 = the round-4 schedules (groups of <= 8 up to 256 rows, segments above).
 static uint32_t sum_ro_groups(size_t n, uint32_t R) {
-    static const size_t onewg = knob_size(LAMPI_AB_ENV("LAMPI_SUM_RO_ONEWG"), (size_t)4096);
-    static const size_t wgs = knob_size(LAMPI_AB_ENV("LAMPI_SUM_RO_WGS"), (size_t)65536);
-    static const bool r5 = knob_on(LAMPI_AB_ENV("LAMPI_SUM_RO_GROUPS"));
-    if (!r5) return R <= 256u && sum_groups(n, min(R, 8u)) > 1 ? min(R, 8u) : 0xFFFFFFFFu;
-    if (onewg && R <= 8u && n >= onewg) return 1u;
+    constexpr size_t kOneWgMin = 4096;  // fewest fragments for one per workgroup
+    constexpr size_t kWgTarget = 65536;
+    if (R <= 8u && n >= kOneWgMin) return 1u;
     uint32_t W = min(R, 8u);
-    while (W < R / 2 && (size_t)n * W < wgs) W *= 2;
+    while (W < R / 2 && (size_t)n * W < kWgTarget) W *= 2;
     W = sum_groups(n, W);
     return W > 1 ? W : 0xFFFFFFFFu;
 }
 
-hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img, int grid,
-                           hipStream_t s, bool plan, uint32_t rows_hint) {
-    (void)grid;
+hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img, hipStream_t s,
+                           bool plan, uint32_t rows_hint) {
     if (n == 0) return hipSuccess;
     if (img && plan && n <= kPlanMax) return launch_planned<true, kSumWv, kSumCap>(d, n, out, img, s);
     if (img && rows_hint == 0 && n < kShapeMin) {  // (small batches: as launch_crc_desc)
@@ -6639,37 +6532,24 @@ hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, co
     }
     const bool one_row = sh.one_row, half = sh.pairs, tiny = sh.all_1k;
     const uint32_t contig = sh.contig_len;
-    // one contiguous run of equal 64 B .. 1 KiB fragments: packed rows, as launch_crc_desc (2 KiB: one per wave reads
-    // faster, as for messages)
-    // (A/B knob LAMPI_PACKED_DESC=0: off, as launch_crc_desc)
-    static const bool packed_desc = knob_on(LAMPI_AB_ENV("LAMPI_PACKED_DESC"));
-    // ... on short-lived 4 KiB workgroups (sum_row4k_desc_kernel; profiles/r06/sum_row4k_desc_ab.txt, against the packed
-    // rows: 1 KiB 72.0 -> 79.9%, 256 B 63.6 -> 75.5%, 64 B 50.5-56.0 -> 60.4-64.3%).  A/B knob LAMPI_SUM_ROW4K_DESC=0: off
-    static const bool row4k_desc = knob_on(LAMPI_AB_ENV("LAMPI_SUM_ROW4K_DESC"));
-    if (img && row4k_desc && rows_hint <= 1 && row4k_len(contig)) {
+    // one contiguous run of equal 64 B .. 1 KiB fragments (2 KiB: one per wave reads faster, as for messages) on
+    // short-lived 4 KiB workgroups (sum_row4k_desc_kernel; profiles/r06/sum_row4k_desc_ab.txt, against packed rows of
+    // config B's kernel, since removed: 1 KiB 72.0 -> 79.9%, 256 B 63.6 -> 75.5%, 64 B 50.5-56.0 -> 60.4-64.3%)
+    if (img && rows_hint <= 1 && row4k_len(contig)) {
         size_t done = 0;
         const hipError_t e = launch_sum_desc_row4k(d, n, out, img, s, contig, &done);
         if (e != hipSuccess) return e;
-        if (done) return done >= n ? hipSuccess : launch_sum_desc(d + done, n - done, out + done, img, grid, s, false, 1u);
+        if (done) return done >= n ? hipSuccess : launch_sum_desc(d + done, n - done, out + done, img, s, false, 1u);
     }
-    if (img && packed_desc && rows_hint <= 1 && row4k_len(contig)) {  // (the same lengths)
-        size_t done = 0;
-        const hipError_t e = launch_desc_packed<true>(d, n, out, img, s, contig, &done);
-        if (e != hipSuccess) return e;
-        if (done) return done >= n ? hipSuccess : launch_sum_desc(d + done, n - done, out + done, img, grid, s, false, 1u);
-    }
-    // (A/B knob LAMPI_SUM_TINY=0, as launch_sum_msg)
-    static const bool sum_tiny = knob_on(LAMPI_AB_ENV("LAMPI_SUM_TINY"));
-    if (img && sum_tiny && tiny && rows_hint <= 1 && n / 256 >= 256) {  // (as launch_sum_msg: 256 per workgroup)
+    if (img && tiny && rows_hint <= 1 && n / 256 >= 256) {  // (as launch_sum_msg: 256 per workgroup)
         hipLaunchKernelGGL((crc_stream_kernel<DescSource, kStreamD, kStreamK, true, kSumWv, kSumCap>),
                            frags_grid(n, 256), dim3(64 * kSumWv), 0, s, DescSource{d}, n, 256u, img, out, nullptr);
         return hipGetLastError();
     }
     // batches the census saw as all <= 2 KiB fragments: one fragment per wave, four to a workgroup
     // (sum_copy_waves_kernel, IB's SUM copies' schedule; profiles/r05/sum_ro_waves_ab.txt: 1,976 B 45.5 -> 69.5%,
-    // 1 KiB 35.6 -> 64.3%, 2 KiB 58.5 -> 80.4%, 256 B 10.2 -> 20.8%).  A/B knob LAMPI_SUM_RO_WAVES=0: off.
-    static const bool ro_waves = knob_on(LAMPI_AB_ENV("LAMPI_SUM_RO_WAVES"));
-    if (img && ro_waves && half && rows_hint <= 1) {
+    // 1 KiB 35.6 -> 64.3%, 2 KiB 58.5 -> 80.4%, 256 B 10.2 -> 20.8%).
+    if (img && half && rows_hint <= 1) {
         launch_sum_copy(DescSource{d}, n, out, s, true);
         return hipGetLastError();
     }
@@ -6685,13 +6565,10 @@ hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, co
         return launch_row_segments<true, kSumWv, kSumCap>(d, n, out, img, s, rows_hint);
     // batches of one-row fragments (the census: every sampled fragment 1-4096 bytes) on short-lived 128-thread
     // workgroups of two fragments each (profiles/r04/sum_ro_wg_ab.txt: 4 KiB descriptors 79.6 -> 86.3%; one per
-    // workgroup 83.2%, four 82.7%; config C's mixed sizes lost 0.5 on it and keep the piece streams).  A/B knob
-    // LAMPI_SUM_RO_WG = fragments per workgroup (0: off).
-    static const uint32_t ro_wg = knob_u32(LAMPI_AB_ENV("LAMPI_SUM_RO_WG"), 2u);
-    if (img && ro_wg && one_row && rows_hint <= 1) {
-        hipLaunchKernelGGL(sum_copy_wg_kernel<DescSource>,
-                           dim3((unsigned)std::min<size_t>((n + ro_wg - 1) / ro_wg, kMaxWgGrid)), dim3(kSumWgThreads), 0,
-                           s, DescSource{d}, n, out);
+    // workgroup 83.2%, four 82.7%; config C's mixed sizes lost 0.5 on it and keep the piece streams).
+    if (img && one_row && rows_hint <= 1) {
+        hipLaunchKernelGGL(sum_copy_wg_kernel<DescSource>, dim3((unsigned)std::min<size_t>((n + 1) / 2, kMaxWgGrid)),
+                           dim3(kSumWgThreads), 0, s, DescSource{d}, n, out);
         return hipGetLastError();
     }
     if (img) {  // piece streams (img: the zero chunk)
@@ -6706,29 +6583,20 @@ hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, co
 }
 
 hipError_t launch_sum_msg(const uint8_t *base, size_t msg_len, size_t frag_len, size_t n, uint32_t *out,
-                          const uint32_t *img, int grid, hipStream_t s) {
-    (void)grid;
+                          const uint32_t *img, hipStream_t s) {
     if (n == 0) return hipSuccess;
     // Messages of >= 256 fragments on short-lived 128-thread workgroups, one fragment each (sum_copy_wg_kernel,
     // the read-only SUM descriptors' shape: VERDICT r4 item 4), whatever the fragment length.  Same box,
     // interleaved rounds (profiles/r05/sum_msg_ab.txt), against the regular kernel / piece streams: config B
     // (4 KiB) 80.2-80.4 -> 87.1-87.3% (two fragments per workgroup 83.7%, four 82.1%); 16 KiB 78-79 -> 86.3%,
     // config D's shard 0 (64 GiB of 16 KiB) 79.8-79.9 -> 86.6-87.2%; 32 KiB 77 -> 86%; GM's 65,456 B 76.6 ->
-    // 84.6%; 1 MiB 77.2 -> 88.4%.  A/B knobs LAMPI_SUM_MSG_WG = fragments per workgroup (0: off),
-    // LAMPI_SUM_MSG_MAX = the longest fragment taken (bytes).
-    static const uint32_t msg_wg = knob_u32(LAMPI_AB_ENV("LAMPI_SUM_MSG_WG"), 1u);
-    static const size_t msg_max = knob_size(LAMPI_AB_ENV("LAMPI_SUM_MSG_MAX"), ~(size_t)0);
-    // fragments of 64 B .. 1 KiB (powers of two) in packed rows of config B's kernel (2 KiB: one per wave reads
-    // faster, below); the message's last fragments through the schedules below
-    // (A/B knob LAMPI_PACKED_SUM = the longest fragment taken, 0: off)
-    static const size_t packed_max = knob_size(LAMPI_AB_ENV("LAMPI_PACKED_SUM"), (size_t)1024);
-    // fragments of 64 B .. 1 KiB (powers of two): one short-lived workgroup per 4 KiB of the message (sum_row4k_kernel),
-    // the message's last fragments (past its last whole 4 KiB) through the schedules below.  Same box, interleaved
-    // (profiles/r06/sum_row4k_ab.txt), against the packed rows: 1 GiB of 1 KiB (config A's shape) 74.0 -> 83.1%, 512 B
-    // 70.9 -> 81.8%, 256 B 67.7 -> 82.0%, 64 B 61.9 -> 76.8%; 16 GiB of 1 KiB 77.3 -> 84.7%.  A/B knob
-    // LAMPI_SUM_ROW4K=0: off (the packed rows below)
-    static const bool row4k = knob_on(LAMPI_AB_ENV("LAMPI_SUM_ROW4K"));
-    if (row4k && row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
+    // 84.6%; 1 MiB 77.2 -> 88.4%.
+    // fragments of 64 B .. 1 KiB (powers of two; 2 KiB: one per wave reads faster, below): one short-lived workgroup per
+    // 4 KiB of the message (sum_row4k_kernel), the message's last fragments (past its last whole 4 KiB) through the
+    // schedules below.  Same box, interleaved (profiles/r06/sum_row4k_ab.txt), against packed rows of config B's kernel
+    // (since removed): 1 GiB of 1 KiB (config A's shape) 74.0 -> 83.1%, 512 B 70.9 -> 81.8%, 256 B 67.7 -> 82.0%, 64 B
+    // 61.9 -> 76.8%; 16 GiB of 1 KiB 77.3 -> 84.7%.
+    if (row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
         const size_t nrow = msg_len / kRowBytes, done = nrow * (kRowBytes / frag_len);
         with_row4k_lanes(frag_len, [&](auto kG) {
             hipLaunchKernelGGL(sum_row4k_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0, s, base, out);
@@ -6736,19 +6604,10 @@ hipError_t launch_sum_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess || done >= n) return e;
         return launch_sum_msg(base + done * frag_len, msg_len - done * frag_len, frag_len, n - done, out + done, img,
-                              grid, s);
-    }
-    if (frag_len <= packed_max) {
-        size_t done = 0;
-        const hipError_t e = launch_packed<true>(base, msg_len, frag_len, 0u, out, nullptr, s, &done);
-        if (e != hipSuccess) return e;
-        if (done >= n && done) return hipSuccess;
-        if (done)
-            return launch_sum_msg(base + done * frag_len, msg_len - done * frag_len, frag_len, n - done, out + done, img,
-                                  grid, s);
+                              s);
     }
     const uint32_t R = (uint32_t)std::min<size_t>((frag_len + kRowBytes - 1) / kRowBytes, 0xFFFFFFFFu);
-    if (msg_wg && frag_len <= msg_max && (n >= 256 || R > 8) && R > 1 && img) {  // (few large fragments too:
+    if ((n >= 256 || R > 8) && R > 1 && img) {  // (few large fragments too:
         // 16 x 16 MiB on the regular kernel, one fragment per chain, read 1.9%)
         // fragments over one row: the read-only descriptors' schedule (sum_ro_groups), as one workgroup
         // per fragment in batches under 4,096 fragments ran a single round of too few workgroups (1 MiB x 1,024
@@ -6761,26 +6620,23 @@ hipError_t launch_sum_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
         }
         if (W < 0xFFFFFFFFu) return launch_sum_copy_groups(src, n, out, s, W);
     }
-    // fragments of at most 2 KiB one per wave (as launch_sum_desc: 1,976 B 51.2 -> 74.9%, 2 KiB 68 -> 84.2%)
-    static const bool ro_waves = knob_on(LAMPI_AB_ENV("LAMPI_SUM_RO_WAVES"));
     // messages of fragments up to 1 KiB: the SUM piece streams with 256 fragments per workgroup (many fragments
     // share a row; profiles/r05/sum_tiny_ab.txt: 64 B 6.5 -> 19.8%, 256 B 22.8 -> 48.6%, 512 B 44.7 -> 67.6%,
-    // 1 KiB 70.2 -> 72.4%).  A/B knob LAMPI_SUM_TINY = the longest fragment taken (0: off).
-    static const uint32_t tiny_max = knob_u32(LAMPI_AB_ENV("LAMPI_SUM_TINY"), 1024u);
-    if (img && frag_len <= tiny_max && n / 256 >= 256) {
+    // 1 KiB 70.2 -> 72.4%).
+    if (img && frag_len <= 1024 && n / 256 >= 256) {
         hipLaunchKernelGGL((crc_stream_kernel<MsgSource, kStreamD, kStreamK, true, kSumWv, kSumCap>),
                            frags_grid(n, 256), dim3(64 * kSumWv), 0, s, MsgSource{base, msg_len, frag_len, 0u}, n, 256u,
                            img, out, nullptr);
         return hipGetLastError();
     }
-    if (ro_waves && frag_len <= kRowBytes / 2 && n >= 256) {
+    // fragments of at most 2 KiB one per wave (as launch_sum_desc: 1,976 B 51.2 -> 74.9%, 2 KiB 68 -> 84.2%)
+    if (frag_len <= kRowBytes / 2 && n >= 256) {
         launch_sum_copy(MsgSource{base, msg_len, frag_len, 0u}, n, out, s, true);
         return hipGetLastError();
     }
-    if (msg_wg && frag_len <= msg_max && n >= 256 && R <= 1) {
-        hipLaunchKernelGGL(sum_copy_wg_kernel<MsgSource>,
-                           dim3((unsigned)std::min<size_t>((n + msg_wg - 1) / msg_wg, kMaxWgGrid)), dim3(kSumWgThreads), 0,
-                           s, MsgSource{base, msg_len, frag_len, 0u}, n, out);
+    if (n >= 256 && R <= 1) {  // one fragment per workgroup
+        hipLaunchKernelGGL(sum_copy_wg_kernel<MsgSource>, dim3((unsigned)std::min<size_t>(n, kMaxWgGrid)),
+                           dim3(kSumWgThreads), 0, s, MsgSource{base, msg_len, frag_len, 0u}, n, out);
         return hipGetLastError();
     }
     if (msg_len != 0 && frag_len % kRowBytes == 0 && msg_len % frag_len == 0 && regular_msg_frag(frag_len, true) &&
@@ -6816,11 +6672,9 @@ static hipError_t launch_crc_light_copy(const uint8_t *base, size_t msg_len, siz
     const uint32_t R = (uint32_t)((frag_len + kRowBytes - 1) / kRowBytes);
     const size_t items = n * R;
     auto launch = [&](uint32_t *o) {
-        with_waves(light_waves(), [&](auto wv) {
-            constexpr int kW = decltype(wv)::value;
-            hipLaunchKernelGGL(crc_light_copy_kernel<kW>, dim3((unsigned)((items + kW - 1) / kW)), dim3(64 * kW), 0, s,
-                               base, msg_len, (uint32_t)frag_len, R, items, partial, dst, dst_stride, img, o);
-        });
+        constexpr int kW = kLightWaves;
+        hipLaunchKernelGGL(crc_light_copy_kernel<kW>, dim3((unsigned)((items + kW - 1) / kW)), dim3(64 * kW), 0, s, base,
+                           msg_len, (uint32_t)frag_len, R, items, partial, dst, dst_stride, img, o);
     };
     if (R == 1) {
         launch(out);
@@ -6879,12 +6733,11 @@ hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len
         // sum_row4k_copy_kernel (its sums land in out and are overwritten), then the read-only CRC of the source in
         // packed rows (launch_crc_msg); the fragments past the last whole 4 KiB through the schedules below.  Same box,
         // interleaved (profiles/r06/crc_copy_2pass_ab.txt), against the one-pass table-light copy, of read + write:
-        // 1 KiB 33.9 -> 52.1%, 256 B 9.0 -> 49.5%, 64 B 2.3 -> 48.4%.  A/B knob LAMPI_CRC_COPY_2PASS=0: off
-        static const bool two_pass = knob_on(LAMPI_AB_ENV("LAMPI_CRC_COPY_2PASS"));
-        if (two_pass && row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
+        // 1 KiB 33.9 -> 52.1%, 256 B 9.0 -> 49.5%, 64 B 2.3 -> 48.4%.
+        if (row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
             const size_t nrow = msg_len / kRowBytes, done = nrow * (kRowBytes / frag_len);
             hipError_t e = launch_sum_row4k_copy(base, nrow, frag_len, dst, dst_stride, out, s);
-            if (e == hipSuccess) e = launch_crc_msg(base, nrow * kRowBytes, frag_len, partial, done, out, img, 0, s);
+            if (e == hipSuccess) e = launch_crc_msg(base, nrow * kRowBytes, frag_len, partial, done, out, img, s);
             if (e != hipSuccess || done >= n) return e;
             return launch_msg_bcopy(base + done * frag_len, msg_len - done * frag_len, frag_len, partial,
                                     dst + done * dst_stride, dst_stride, n - done, out + done, mode, img, s);
@@ -6899,9 +6752,8 @@ hipError_t launch_msg_bcopy(const uint8_t *base, size_t msg_len, size_t frag_len
     // SUM copies of 64 B .. 1 KiB fragments (powers of two): one short-lived workgroup per 4 KiB of the message
     // (sum_row4k_copy_kernel), the fragments past the last whole 4 KiB through the schedules below.  Same box,
     // interleaved (profiles/r06/sum_row4k_copy_ab.txt), against one workgroup per fragment, of read + write: 1 KiB
-    // 56.4 -> 79.3%, 256 B 17.2 -> 78.2%, 64 B 5.0 -> 79.2%.  A/B knob LAMPI_SUM_ROW4K_COPY=0: off
-    static const bool row4k_copy = knob_on(LAMPI_AB_ENV("LAMPI_SUM_ROW4K_COPY"));
-    if (row4k_copy && mode == LAMPI_CSUM_SUM32 && row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
+    // 56.4 -> 79.3%, 256 B 17.2 -> 78.2%, 64 B 5.0 -> 79.2%.
+    if (mode == LAMPI_CSUM_SUM32 && row4k_len(frag_len) && row4k_rows(msg_len / kRowBytes)) {
         const size_t nrow = msg_len / kRowBytes, done = nrow * (kRowBytes / frag_len);
         const hipError_t e = launch_sum_row4k_copy(base, nrow, frag_len, dst, dst_stride, out, s);
         if (e != hipSuccess || done >= n) return e;
@@ -6985,8 +6837,6 @@ hipError_t launch_scatter_u32(const uint32_t *vals, size_t n, uint8_t *dst, size
 //   every wave's prologue -- 262,144 x 1,976 bytes 0.2358 ms fused, 0.2060 ms in two launches (A 0.2266);
 //   row groups (GM's 65,456-byte payloads, learned or hinted): the join kernel's emitting lanes gather the prefix
 //   from the global tables -- 16,384 x 65,456 bytes 0.3999 ms fused, 0.3837 ms in two launches (A 0.3899).
-// A/B knob LAMPI_SEND_FUSED: 0 = every batch through launch_bcopy_desc into pooled scratch, then send_stamp_kernel
-// (the message form's route); 1 = every batch fused, the pair kernel and the CRC join too.
 // The Quadrics kind: always two launches, because an inline payload lands in bytes the header checksum reads --
 // launch_fused_copy over QSendSource with the checksums in pooled scratch (checksumming off: the plain copy
 // schedules over QSendCopyOnlySource), then qsend_stamp_kernel.  Shapes are learned in records of its own kinds.
@@ -7016,23 +6866,6 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
     if (n == 0) return hipSuccess;
     if (!img) return hipErrorInvalidValue;
     if (kind == LAMPI_SEND_HDR_QUADRICS) return launch_qsend_pack(d, n, hdrs, hdr_stride, mode, img, s, rows_hint);
-    static const int fused = [] {  // 0: two launches, 1: as measured, 2: fused everywhere
-        const char *e = LAMPI_AB_ENV("LAMPI_SEND_FUSED");
-        return !e ? 1 : e[0] == '0' ? 0 : 2;
-    }();
-    // batch(vals): a launch writing the n checksums to scratch; then the stamp
-    auto two_launches = [&](auto &&batch) {
-        uint32_t *vals = nullptr;
-        hipError_t e = stream_vals(s, n, &vals);
-        if (e != hipSuccess) return e;
-        e = batch(vals);
-        if (e == hipSuccess && !(mode == LAMPI_CSUM_NONE && kind == LAMPI_SEND_HDR_GM))
-            e = launch_per_item(send_stamp_kernel<false>, n, s, hdrs, hdr_stride, (uint32_t)n, (const uint32_t *)vals, d,
-                                SendFill{}, (size_t)0, (size_t)0, kind, mode, img);
-        return e;
-    };
-    if (fused == 0)
-        return two_launches([&](uint32_t *vals) { return launch_bcopy_desc(d, n, vals, mode, img, s, rows_hint); });
     if (mode == LAMPI_CSUM_NONE) {
         SendCopyOnlySource co;
         static_cast<SendSource &>(co) = SendSource{d, hdrs, hdr_stride, img, kind, mode};
@@ -7042,9 +6875,17 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
     const bool crc = mode == LAMPI_CSUM_CRC32;
     const SendSource src{d, hdrs, hdr_stride, img, kind, mode};
     const LearnedShape sh = learn_shape(src, n, s, kShapeSendPack, rows_hint, shape_opts(mode));
-    // the two CRC classes of two launches (above): the same schedule on CopySource, its values to scratch
-    if (crc && fused != 2 && (sh.pairs || runs_as_groups(crc, n, sh)))
-        return two_launches([&](uint32_t *vals) { return launch_fused_copy(CopySource{d}, crc, n, img, vals, s, sh); });
+    // the two CRC classes of two launches (above): the same schedule on CopySource, its values to scratch, then the stamp
+    if (crc && (sh.pairs || runs_as_groups(crc, n, sh))) {
+        uint32_t *vals = nullptr;
+        hipError_t e = stream_vals(s, n, &vals);
+        if (e != hipSuccess) return e;
+        e = launch_fused_copy(CopySource{d}, crc, n, img, vals, s, sh);
+        if (e == hipSuccess)
+            e = launch_per_item(send_stamp_kernel<false>, n, s, hdrs, hdr_stride, (uint32_t)n, (const uint32_t *)vals, d,
+                                SendFill{}, (size_t)0, (size_t)0, kind, mode, img);
+        return e;
+    }
     return launch_fused_copy(src, crc, n, img, nullptr, s, sh);
 }
 
@@ -7056,14 +6897,14 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
 // sender's fragments that are not copied): the regular kernel for whole-4-KiB-row fragments at a 16-byte-aligned
 // base, the piece streams otherwise.
 hipError_t launch_msg_csum(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
-                           int mode, const uint32_t *img, int grid, hipStream_t s) {
+                           int mode, const uint32_t *img, hipStream_t s) {
     const size_t n = msg_len ? (msg_len + frag_len - 1) / frag_len : 1;
-    if (mode == LAMPI_CSUM_SUM32) return launch_sum_msg(base, msg_len, frag_len, n, out, img, grid, s);
+    if (mode == LAMPI_CSUM_SUM32) return launch_sum_msg(base, msg_len, frag_len, n, out, img, s);
     const bool regular = msg_len != 0 && frag_len % kRowBytes == 0 && msg_len % frag_len == 0 &&
                          regular_msg_frag(frag_len, false) && ((uintptr_t)base & 15u) == 0 &&
                          !crc_light_msg(frag_len, msg_len);
-    if (regular) return launch_crc_regular(base, n, frag_len, partial, out, img, grid, s);
-    return launch_crc_msg(base, msg_len, frag_len, partial, n, out, img, grid, s);
+    if (regular) return launch_crc_regular(base, n, frag_len, partial, out, img, s);
+    return launch_crc_msg(base, msg_len, frag_len, partial, n, out, img, s);
 }
 
 // The Quadrics kind of the message form: the first launch leaves the fragments' checksums in vals, the stamp builds
@@ -7075,7 +6916,7 @@ hipError_t launch_msg_csum(const uint8_t *base, size_t msg_len, size_t frag_len,
 //   is left out of the copy and checksummed by a read-only launch of its own.
 static hipError_t launch_qmsg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
                                         size_t slot_stride, const SendFill &f, size_t n, int mode, const uint32_t *img,
-                                        int grid, hipStream_t s) {
+                                        hipStream_t s) {
     uint32_t *vals = nullptr;
     hipError_t e = stream_vals(s, n, &vals);
     if (e != hipSuccess) return e;
@@ -7088,7 +6929,7 @@ static hipError_t launch_qmsg_send_pack(const uint8_t *base, size_t msg_len, siz
     }
     if (msg_len != 0) {
         if (frag_len <= kQInline || bare) {
-            if (!none) e = launch_msg_csum(base, msg_len, frag_len, kCrcInit, vals, mode, img, grid, s);
+            if (!none) e = launch_msg_csum(base, msg_len, frag_len, kCrcInit, vals, mode, img, s);
         } else {
             const size_t last = msg_len - (n - 1) * frag_len;
             const size_t nfull = last <= kQInline ? n - 1 : n;
@@ -7096,7 +6937,7 @@ static hipError_t launch_qmsg_send_pack(const uint8_t *base, size_t msg_len, siz
                 e = launch_msg_bcopy(base, std::min(msg_len, nfull * frag_len), frag_len, kCrcInit, ring + kQHdrBytes,
                                      slot_stride, nfull, vals, none ? LAMPI_CSUM_SUM32 : mode, img, s);
             if (e == hipSuccess && nfull < n && !none)
-                e = launch_msg_csum(base + nfull * frag_len, last, last, kCrcInit, vals + nfull, mode, img, grid, s);
+                e = launch_msg_csum(base + nfull * frag_len, last, last, kCrcInit, vals + nfull, mode, img, s);
         }
     }
     if (e == hipSuccess)
@@ -7120,12 +6961,12 @@ static SendFill send_fill(const lampi_send_hdr_fill &fill) {
 
 hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
                                 size_t slot_stride, const lampi_send_hdr_fill &fill, size_t n, int kind, int mode,
-                                const uint32_t *img, hipStream_t s, int grid) {
+                                const uint32_t *img, hipStream_t s) {
     if (n == 0) return hipSuccess;
     if (!img) return hipErrorInvalidValue;
     const SendFill f = send_fill(fill);
     if (kind == LAMPI_SEND_HDR_QUADRICS)
-        return launch_qmsg_send_pack(base, msg_len, frag_len, ring, slot_stride, f, n, mode, img, grid, s);
+        return launch_qmsg_send_pack(base, msg_len, frag_len, ring, slot_stride, f, n, mode, img, s);
     uint32_t *vals = nullptr;
     hipError_t e = stream_vals(s, n, &vals);
     if (e != hipSuccess) return e;

@@ -36,20 +36,20 @@ hipError_t diag_stream_timeline(const lampi_frag_desc *d, size_t n, uint32_t *ou
                                 uint64_t *stamps, hipStream_t s, uint32_t *nwg);
 hipError_t diag_regular_timeline(const uint8_t *base, size_t n, uint32_t *out, const uint32_t *img, uint64_t *stamps,
                                  hipStream_t s, uint32_t *nwg);
-hipError_t launch_crc_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img, int grid,
-                           hipStream_t s, bool plan = false, uint32_t rows_hint = 1);
+hipError_t launch_crc_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img, hipStream_t s,
+                           bool plan = false, uint32_t rows_hint = 1);
 // One wavefront per fragment (crc_rows_kernel / sum_rows_kernel), mode = lampi_csum_mode.
 hipError_t launch_desc_per_wave(const lampi_frag_desc *d, size_t n, uint32_t *out, int mode, const uint32_t *img,
                                 hipStream_t s);
 hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, size_t n,
-                          uint32_t *out, const uint32_t *img, int grid, hipStream_t s);
+                          uint32_t *out, const uint32_t *img, hipStream_t s);
 // Checksums of the fragments of a contiguous device-resident message, not copied (one for an empty message): the
 // regular kernel for whole-4-KiB-row fragments at a 16-byte-aligned base, the piece streams otherwise.
 hipError_t launch_msg_csum(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
-                           int mode, const uint32_t *img, int grid, hipStream_t s);
+                           int mode, const uint32_t *img, hipStream_t s);
 // Regular batch: frag_len % 4096 == 0, base 16-byte aligned, n full fragments.
 hipError_t launch_crc_regular(const uint8_t *base, size_t n, size_t frag_len, uint32_t partial, uint32_t *out,
-                              const uint32_t *img, int grid, hipStream_t s);
+                              const uint32_t *img, hipStream_t s);
 // Fused copy + checksum (bcopy_uicrc / bcopy_uicsum per descriptor), mode = lampi_csum_mode (NONE: copies only,
 // out = n words of scratch).
 // rows_hint (LAMPI_CSUM_ROWS_HINT): row groups per fragment, 1 = one wave (SUM: workgroup) walks every row
@@ -70,12 +70,12 @@ hipError_t launch_send_pack(const lampi_copy_desc *d, size_t n, uint8_t *hdrs, s
 // header from `fill` (host memory, read here) and stamps it.
 // kind LAMPI_SEND_HDR_QUADRICS (both forms): 128-byte headers, a fragment of at most 52 bytes placed in the header
 // at +72, longer ones at ring + 128 + k*slot_stride or, with slot_stride == 128, checksummed only by the read-only
-// message kernels (grid = crc_grid(device), used by this kind alone); always the copy or checksum launch, then one
+// message kernels; always the copy or checksum launch, then one
 // stamp launch (ref src/path/quadrics/sendFrag.h:766-880) -- except the message form with checksumming off and
 // fragments of 53 bytes .. one row, whose copy workgroups write the envelopes themselves.
 hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag_len, uint8_t *ring,
                                 size_t slot_stride, const lampi_send_hdr_fill &fill, size_t n, int kind, int mode,
-                                const uint32_t *img, hipStream_t s, int grid = 0);
+                                const uint32_t *img, hipStream_t s);
 // RecvDesc_t::CopyToApp per descriptor (copy min(length, app_len), checksum length, verify).
 hipError_t launch_copy_to_app(const lampi_recv_desc *d, size_t n, const uint8_t *expected, size_t exp_stride,
                               int64_t *copied, uint32_t *csum, uint32_t *mask, uint32_t *nbad, int mode,
@@ -154,10 +154,10 @@ hipError_t launch_sum64_finish(const uint64_t *vals, uint32_t nv, const uint8_t 
                                uint64_t seq = 0);
 // SUM per descriptor / per fragment of a message: piece streams when img (the table image, for its
 // zero chunk) is given, one wavefront per fragment (sum_rows_kernel) otherwise.
-hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img, int grid,
-                           hipStream_t s, bool plan = false, uint32_t rows_hint = 1);
+hipError_t launch_sum_desc(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img, hipStream_t s,
+                           bool plan = false, uint32_t rows_hint = 1);
 hipError_t launch_sum_msg(const uint8_t *base, size_t msg_len, size_t frag_len, size_t n, uint32_t *out,
-                          const uint32_t *img, int grid, hipStream_t s);
+                          const uint32_t *img, hipStream_t s);
 hipError_t launch_crc_combine(const uint32_t *vals, uint32_t n, const uint32_t *tabs, uint32_t npow,
                               uint32_t *out, hipStream_t s, uint64_t *sig = nullptr, uint64_t seq = 0);
 hipError_t launch_sum_finish(const uint32_t *partials, uint32_t npart, const uint8_t *src, uint64_t len,

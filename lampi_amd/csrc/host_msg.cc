@@ -200,7 +200,7 @@ hipError_t host_msg(const uint8_t *h_msg, size_t msg_len, size_t frag_len, size_
         TRY(hipMemcpyAsync(d, h_msg + off, nb, hipMemcpyHostToDevice, p.s_in));
         TRY(hipEventRecord(p.in_done[b], p.s_in));
         TRY(hipStreamWaitEvent(p.s_k, p.in_done[b], 0));
-        if (!none) TRY(launch_msg_csum(d, nb, frag_len, partial, dres + f0, mode, img, crc_grid(p.dev), p.s_k));
+        if (!none) TRY(launch_msg_csum(d, nb, frag_len, partial, dres + f0, mode, img, p.s_k));
         TRY(hipEventRecord(p.k_done[b], p.s_k));
         if (!copy) continue;
         TRY(hipStreamWaitEvent(p.s_out, p.in_done[b], 0));

@@ -384,7 +384,6 @@ void wait_done(HostCtx &c, uint64_t seq) {
 uint32_t device_crc(HostCtx &c, const Staged &st, uint64_t len, uint32_t partial) {
     const uint32_t *img = nullptr;
     LAMPI_CHECK(device_tables(c.dev, &img));
-    const int grid = crc_grid(c.dev);
     // zero-copy calls above 8 KiB: 4 KiB pieces folded by the combine kernel (one piece per row:
     // the piece-stream kernel then joins no fragment across its chains, whose serial join of a
     // 64 KiB piece cost ~20 us); otherwise pieces of piece_size
@@ -404,11 +403,11 @@ uint32_t device_crc(HostCtx &c, const Staged &st, uint64_t len, uint32_t partial
         LAMPI_CHECK(launch_host_one(st.base, (uint32_t)len, partial, res, LAMPI_CSUM_CRC32, img, c.stream,
                                     signal_word(c, seq), seq));
     } else if (n == 1) {
-        LAMPI_CHECK(launch_crc_desc(upload_descs(c, 1, false), 1, res, img, grid, c.stream, false, 1u));
+        LAMPI_CHECK(launch_crc_desc(upload_descs(c, 1, false), 1, res, img, c.stream, false, 1u));
     } else {
         ensure(c.dvals, c.vcap, (size_t)n + 4);
         // (rows hint 1: pieces sized for the count split, not a small batch of unknown fragments)
-        LAMPI_CHECK(launch_crc_desc(upload_descs(c, n, st.zero_copy), n, c.dvals, img, grid, c.stream, false, 1u));
+        LAMPI_CHECK(launch_crc_desc(upload_descs(c, n, st.zero_copy), n, c.dvals, img, c.stream, false, 1u));
         LAMPI_CHECK(launch_crc_combine(c.dvals, n, combine_tables(c, B), next_pow2(n), res, c.stream,
                                        signal_word(c, seq), seq));
     }
@@ -418,7 +417,6 @@ uint32_t device_crc(HostCtx &c, const Staged &st, uint64_t len, uint32_t partial
 
 // uicsum of the staged bytes [0, len) with chaining state, computed on the GPU.
 uint32_t device_sum(HostCtx &c, const Staged &st, uint64_t len, unsigned int *pint, unsigned int *plen) {
-    const int grid = crc_grid(c.dev);
     const uint32_t k = *plen >= 4 ? 0u : *plen;
     const uint64_t head = k ? std::min<uint64_t>(4 - k, len) : 0;
     const uint64_t body = (len - head) & ~3ull;
@@ -442,7 +440,7 @@ uint32_t device_sum(HostCtx &c, const Staged &st, uint64_t len, unsigned int *pi
     }
     if (n) {
         const lampi_frag_desc *d = upload_descs(c, n, st.zero_copy);
-        LAMPI_CHECK(launch_sum_desc(d, n, c.dvals, nullptr, grid, c.stream, false, 1u));
+        LAMPI_CHECK(launch_sum_desc(d, n, c.dvals, nullptr, c.stream, false, 1u));
     }
     LAMPI_CHECK(launch_sum_finish(c.dvals, n, st.base, len, *pint, *plen, out3, c.stream, signal_word(c, seq), seq));
     wait_done(c, seq);
@@ -631,8 +629,8 @@ int lampi_frag_csum_batch(const lampi_frag_desc *d_descs, size_t n, uint32_t *d_
     if (c.err != hipSuccess) return to_int(c.err);
     hipStream_t s = (hipStream_t)stream;
     if (mode == LAMPI_CSUM_SUM32)
-        return to_int(launch_sum_desc(d_descs, n, d_out, c.img, crc_grid(c.dev), s, by_bytes, rows_hint));
-    return to_int(launch_crc_desc(d_descs, n, d_out, c.img, crc_grid(c.dev), s, by_bytes, rows_hint));
+        return to_int(launch_sum_desc(d_descs, n, d_out, c.img, s, by_bytes, rows_hint));
+    return to_int(launch_crc_desc(d_descs, n, d_out, c.img, s, by_bytes, rows_hint));
 }
 
 // Internal diagnostic (not in include/lampi_csum.h): the read-only CRC piece-stream kernel's timeline,
@@ -766,7 +764,7 @@ int lampi_msg_csum(const void *d_msg, size_t msg_len, size_t frag_len, uint32_t 
     const DeviceCall c = device_call();
     if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_msg_csum((const uint8_t *)d_msg, msg_len, frag_len, partial, d_out, mode, c.img,
-                                  crc_grid(c.dev), (hipStream_t)stream));
+                                  (hipStream_t)stream));
 }
 
 int lampi_msg_bcopy_strided(const void *d_msg, size_t msg_len, size_t frag_len, void *d_dst, size_t dst_stride,
@@ -832,7 +830,7 @@ int lampi_msg_send_pack(const void *d_msg, size_t msg_len, size_t frag_len, void
     const DeviceCall c = device_call();
     if (c.err != hipSuccess) return to_int(c.err);
     return to_int(launch_msg_send_pack((const uint8_t *)d_msg, msg_len, frag_len, (uint8_t *)d_ring, slot_stride, *h_fill,
-                                       n, hdr_kind, mode, c.img, (hipStream_t)stream, crc_grid(c.dev)));
+                                       n, hdr_kind, mode, c.img, (hipStream_t)stream));
 }
 
 // The send step through a typemap (ref src/path/gm/sendFrag.cc:157-217, src/path/ib/sendFrag.cc:140-203): no

@@ -261,25 +261,45 @@ def test_mode_flag_macros_match_the_binding(tmp_path):
         rows_hint_bits(4096)
 
 
+RETIRED_KNOBS = [
+    "LAMPI_PAIR_WAVES", "LAMPI_LIGHT_WAVES", "LAMPI_STREAM_FPG", "LAMPI_SHAPES_UNKEYED", "LAMPI_DESC_FPW",
+    "LAMPI_SMALL_BATCH", "LAMPI_PACKED_DESC", "LAMPI_CRC_RO_PAIRS", "LAMPI_CRC_DESC_REGULAR", "LAMPI_PACKED",
+    "LAMPI_PACKED_FPW", "LAMPI_SUM_CP_GRP_MIN", "LAMPI_SUM_CP_GRP_ROWS", "LAMPI_SUM_ROW4K_COPY_DESC",
+    "LAMPI_RECV_PREPASS", "LAMPI_SUM_RO_ONEWG", "LAMPI_SUM_RO_WGS", "LAMPI_SUM_RO_GROUPS", "LAMPI_SUM_ROW4K_DESC",
+    "LAMPI_SUM_TINY", "LAMPI_SUM_RO_WAVES", "LAMPI_SUM_RO_WG", "LAMPI_SUM_MSG_WG", "LAMPI_SUM_MSG_MAX",
+    "LAMPI_PACKED_SUM", "LAMPI_SUM_ROW4K", "LAMPI_CRC_COPY_2PASS", "LAMPI_SUM_ROW4K_COPY", "LAMPI_SEND_FUSED",
+]
+
+
 def test_default_library_reads_no_ab_knobs():
-    """the schedule knobs measured in A/B runs are compiled only into the A/B build
-    (make AB=1 -> liblampi_csum_ab.so, LAMPI_AB_KNOBS); the default library's dispatch depends on no
-    environment variable but the documented switches (LAMPI_CSUM_NO_SHAPES, LAMPI_HOST_CHUNK_BYTES) -- none of
-    the knob names is in its binary, and every getenv in the sources goes through LAMPI_AB_ENV or is documented."""
+    """the library's dispatch depends on no environment variable but the documented switches
+    (LAMPI_CSUM_NO_SHAPES, LAMPI_HOST_CHUNK_BYTES).  The 29 schedule knobs once measured in A/B runs are retired,
+    each folded to its measured value (DESIGN.md has the table): none of their names is in the sources, the Makefile
+    or the binary, the mechanism that read them (LAMPI_AB_ENV / LAMPI_AB_KNOBS) is gone, and every getenv in the
+    sources names a documented switch literally."""
+    assert len(RETIRED_KNOBS) == 29 and len(set(RETIRED_KNOBS)) == 29
     csrc = os.path.join(ROOT, "lampi_amd", "csrc")
-    knobs, documented = set(), {"LAMPI_CSUM_NO_SHAPES", "LAMPI_HOST_CHUNK_BYTES"}
-    for name in os.listdir(csrc):
-        if not name.endswith((".hip", ".cc", ".h")):
+    documented = {"LAMPI_CSUM_NO_SHAPES", "LAMPI_HOST_CHUNK_BYTES"}
+    read = set()
+    for name in sorted(os.listdir(csrc)):
+        if not (name.endswith((".hip", ".cc", ".h")) or name == "Makefile"):
             continue
         src = open(os.path.join(csrc, name)).read()
-        knobs |= set(re.findall(r'LAMPI_AB_ENV\("([A-Z0-9_]+)"\)', src))
-        direct = set(re.findall(r'getenv\("([A-Z0-9_]+)"\)', src))
-        assert direct <= documented, (name, direct - documented)
-    assert len(knobs) >= 20, knobs
+        for word in ("LAMPI_AB_ENV", "LAMPI_AB_KNOBS"):
+            assert word not in src, (name, word)
+        present = [k for k in RETIRED_KNOBS if k in src]
+        assert not present, (name, present)
+        if name == "Makefile":
+            continue
+        literal = re.findall(r'getenv\("([A-Z0-9_]+)"\)', src)
+        assert set(literal) <= documented, (name, set(literal) - documented)
+        assert src.count("getenv") == len(literal), (name, "a getenv whose name is not a literal")
+        read |= set(literal)
+    assert read == documented, read
     import lampi_amd
 
     blob = open(lampi_amd._lib.LIB_PATH, "rb").read()
-    present = sorted(k for k in knobs if k.encode() in blob)
+    present = sorted(k for k in RETIRED_KNOBS if k.encode() in blob)
     assert not present, present
     for k in documented:
         assert k.encode() in blob, k

@@ -100,7 +100,7 @@ int main(int argc, char **argv) {
         const uint32_t n = (uint32_t)(bytes / L);
         std::vector<uint32_t> &w = L == 4096 ? want4 : want16;
         w.resize(n);
-        CK(launch_crc_regular(buf, n, L, 0xFFFFFFFFu, out, dimg, 256, 0));
+        CK(launch_crc_regular(buf, n, L, 0xFFFFFFFFu, out, dimg, 0));
         CK(hipMemcpy(w.data(), out, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
     for (Cfg &c : cfgs) {  // correctness once per configuration

@@ -10,9 +10,6 @@ lampi_msg_recv_unpack), whole rings on one stream, device events, 5 warm-ups and
       library built from the parent commit (--lib-a PATH, loaded through LAMPI_CSUM_LIB); with checksumming off
       the copy alone
   B   lampi_recv_unpack_batch (form desc) and lampi_msg_recv_unpack (form msg) from this tree's library
-  B0  both forms with LAMPI_RECV_PREPASS=0 from the A/B build (make -C lampi_amd/csrc AB=1): every header tested
-      inside the copy kernels
-  B2  ... with LAMPI_RECV_PREPASS=2: every header tested by the pre-pass launch
 
 All lines call the C ABI with outputs allocated once.  Every line runs in a fresh child process under its own time
 limit; the lines alternate five times and a child that fails or runs out of time stops the rest.  The table (median
@@ -20,7 +17,7 @@ of the five, A's spread = max - min of its five, shares of 8 TB/s) goes to --out
 profiles/r08/recv_unpack_ab.txt).
 
 python tools/microbench/recv_unpack_ab.py --lib-a /path/to/parent/liblampi_csum.so [--out FILE] [--rounds 5]
-                                          [--lines A,B,B0,B2]
+                                          [--lines A,B]
 """
 import json
 import os
@@ -123,20 +120,15 @@ def drive():
     lib_a = arg("--lib-a")
     if not lib_a or not os.path.exists(lib_a):
         sys.exit("--lib-a: the parent commit's liblampi_csum.so is required for line A")
-    lines = arg("--lines", "A,B,B0,B2").split(",")
-    lib_ab = os.path.join(ROOT, "lampi_amd", "liblampi_csum_ab.so")
-    if any(x in ("B0", "B2") for x in lines) and not os.path.exists(lib_ab):
-        sys.exit(f"{lib_ab} missing: make -C lampi_amd/csrc AB=1")
+    lines = arg("--lines", "A,B").split(",")
     out = arg("--out", os.path.join(ROOT, "profiles", "r08", "recv_unpack_ab.txt"))
     rounds = int(arg("--rounds", "5"))
-    envs = {"A": {"LAMPI_CSUM_LIB": os.path.abspath(lib_a)}, "B": {},
-            "B0": {"LAMPI_CSUM_LIB": lib_ab, "LAMPI_RECV_PREPASS": "0"},
-            "B2": {"LAMPI_CSUM_LIB": lib_ab, "LAMPI_RECV_PREPASS": "2"}}
+    envs = {"A": {"LAMPI_CSUM_LIB": os.path.abspath(lib_a)}, "B": {}}
     times = {}  # (shape, mode) -> column -> [(ms, bytes)]
     failed = None
     for r in range(rounds):
         for line in lines:
-            env = {k: v for k, v in os.environ.items() if k not in ("LAMPI_CSUM_LIB", "LAMPI_RECV_PREPASS")}
+            env = {k: v for k, v in os.environ.items() if k != "LAMPI_CSUM_LIB"}
             env.update(envs[line])
             try:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", line], env=env,
@@ -159,7 +151,7 @@ def drive():
     rows = ["receive step A/B: median ms of %d fresh processes per line (share of 8 TB/s; bytes = payload read + written "
             "+ 72 per slot)" % rounds,
             "A = header check / compare + copy_to_app_batch (parent commit's library, no host read-back); B = "
-            "recv_unpack_batch (desc) / msg_recv_unpack (msg); B0 / B2 = LAMPI_RECV_PREPASS=0 / 2 (A/B build); "
+            "recv_unpack_batch (desc) / msg_recv_unpack (msg); "
             "spread = max - min of A's repeats; * = behind A by more than that",
             f"{'shape':5s} {'mode':4s} " + " ".join(f"{c:>17s}" for c in cols) + f" {'A spread':>9s}"]
     for key in sorted(times):

@@ -8,10 +8,8 @@ lampi_msg_send_pack), whole rings on one stream, device events, 5 warm-ups and 2
   A   msg_bcopy_strided / frag_bcopy_batch_strided, then header_csum_batch_strided -- from a library built from the
       parent commit (--lib-a PATH, loaded through LAMPI_CSUM_LIB)
   B   msg_send_pack / send_pack_batch from this tree's library
-  B0  send_pack_batch with LAMPI_SEND_FUSED=0 from the A/B build (make -C lampi_amd/csrc AB=1): the copy into pooled
-      scratch, then the stamp kernel
 
-Every line runs in a fresh child process under its own time limit; the lines alternate A, B, B0 five times and a
+Every line runs in a fresh child process under its own time limit; the lines alternate A, B five times and a
 child that fails or runs out of time stops the rest.  The table (median of the five, A's spread = max - min of its
 five, shares of 8 TB/s) goes to --out (default profiles/r07/send_pack_ab.txt).
 
@@ -80,12 +78,10 @@ def child(line):
                     dv.header_csum_batch_strided(ring, n, slot, HDR - 4, 18, ring, slot, offset=68, mode=mode)
 
                 runs = {"msg": a_msg, "desc": a_desc}
-            elif line == "B":
+            else:
                 runs = {"msg": lambda: dv.msg_send_pack(msg, L, ring, slot, tmpl, frag_seq0=1, frag_seq_step=1,
                                                         desc_ptr0=4096, desc_ptr_stride=256, kind=kind, mode=mode),
                         "desc": lambda: dv.send_pack_batch(descs, ring, slot, kind=kind, mode=mode)}
-            else:
-                runs = {"desc": lambda: dv.send_pack_batch(descs, ring, slot, kind=kind, mode=mode)}
             for form, run in runs.items():
                 ms = timed(run)
                 print(json.dumps({"line": line, "shape": shape, "form": form, "mode": mname, "ms": ms,
@@ -98,18 +94,14 @@ def drive():
     lib_a = arg("--lib-a")
     if not lib_a or not os.path.exists(lib_a):
         sys.exit("--lib-a: the parent commit's liblampi_csum.so is required for line A")
-    lib_ab = os.path.join(ROOT, "lampi_amd", "liblampi_csum_ab.so")
-    if not os.path.exists(lib_ab):
-        sys.exit(f"{lib_ab} missing: make -C lampi_amd/csrc AB=1")
     out = arg("--out", os.path.join(ROOT, "profiles", "r07", "send_pack_ab.txt"))
     rounds = int(arg("--rounds", "5"))
-    envs = {"A": {"LAMPI_CSUM_LIB": os.path.abspath(lib_a)}, "B": {},
-            "B0": {"LAMPI_CSUM_LIB": lib_ab, "LAMPI_SEND_FUSED": "0"}}
+    envs = {"A": {"LAMPI_CSUM_LIB": os.path.abspath(lib_a)}, "B": {}}
     times = {}  # (shape, form, mode) -> line -> [ms]
     failed = None
     for r in range(rounds):
-        for line in ("A", "B", "B0"):
-            env = {k: v for k, v in os.environ.items() if k not in ("LAMPI_CSUM_LIB", "LAMPI_SEND_FUSED")}
+        for line in ("A", "B"):
+            env = {k: v for k, v in os.environ.items() if k != "LAMPI_CSUM_LIB"}
             env.update(envs[line])
             try:
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", line], env=env,
@@ -130,9 +122,9 @@ def drive():
             break
     rows = ["send step A/B: median ms of %d fresh processes per line (share of 8 TB/s; bytes = payload read + written "
             "+ 72 per slot)" % rounds,
-            "A = bcopy_strided + header_csum_batch_strided (parent commit's library), B = the one-call form, "
-            "B0 = descriptor form with LAMPI_SEND_FUSED=0 (A/B build); spread = max - min of A's repeats",
-            f"{'shape':5s} {'form':4s} {'mode':4s} {'A ms':>16s} {'A spread':>9s} {'B ms':>16s} {'B0 ms':>16s}  verdict"]
+            "A = bcopy_strided + header_csum_batch_strided (parent commit's library), B = the one-call form; "
+            "spread = max - min of A's repeats",
+            f"{'shape':5s} {'form':4s} {'mode':4s} {'A ms':>16s} {'A spread':>9s} {'B ms':>16s}  verdict"]
     for key in sorted(times):
         t = times[key]
 
@@ -144,16 +136,13 @@ def drive():
 
         a, ca = cell("A")
         b, cb = cell("B")
-        b0, cb0 = cell("B0")
         spread = max(m for m, _ in t["A"]) - min(m for m, _ in t["A"]) if "A" in t else 0.0
         verdict = ""
         if a is not None and b is not None:
             verdict = "B meets" if b <= a + spread else "B misses"
-            if b0 is not None:
-                verdict += ", B0 meets" if b0 <= a + spread else ", B0 misses"
-        rows.append(f"{key[0]:5s} {key[1]:4s} {key[2]:4s} {ca} {spread:9.4f} {cb} {cb0}  {verdict}")
+        rows.append(f"{key[0]:5s} {key[1]:4s} {key[2]:4s} {ca} {spread:9.4f} {cb}  {verdict}")
     for key in sorted(times):
-        for line in ("A", "B", "B0"):
+        for line in ("A", "B"):
             if line in times[key]:
                 rows.append(f"raw {key[0]} {key[1]} {key[2]} {line}: " + " ".join(f"{m:.4f}" for m, _ in times[key][line]))
     if failed:
