@@ -666,6 +666,66 @@ int lampi_chain_copy_to_app_batch(const lampi_copy_desc *d_pieces, size_t npiece
                                   uint32_t *d_csum, uint32_t *d_mask, uint32_t *d_nbad, int mode, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Host-memory forms of the one-call send and receive steps.
+ *
+ * The same two steps for a message and a NIC ring in HOST memory (page-locked or pageable), as the host-memory
+ * paths above: synchronous, on the calling thread's own streams, chunked so that chunk i + 1 crosses PCIe while
+ * chunk i is packed or delivered.  They write what the device forms write: the tables of the send step and the
+ * results of the receive step above are the contract, hdr_kind and mode as there (LAMPI_SEND_HDR_GM, _IB,
+ * _QUADRICS; CRC32, SUM32, NONE -- any other bit in mode is refused).  Return 0 or a hipError_t; invalid arguments
+ * return hipErrorInvalidValue before anything is written.
+ * ---------------------------------------------------------------------------------- */
+
+/* Send: gmSendFragDesc::init for fragments [k_first, k_first + k_count) of a host message (fragmented as
+ * lampi_host_msg_bcopy does; msg_len == 0: one empty fragment, its header still written).  Fragment
+ * k = k_first + i goes to the slot at h_ring + i*slot_stride, and the slot's bytes are exactly what
+ * lampi_msg_send_pack writes for fragment k OF THE WHOLE MESSAGE: h_fill's series are indexed by the absolute k
+ * (frag_seq0 + k*frag_seq_step, desc_ptr0 + k*desc_ptr_stride, seq_offset0 + k*frag_len, Quadrics' dataElanAddr
+ * tmpl's + k*frag_len mod 2^32), so a message packed by several gated calls (gm/path.cc:104-118) gets the ring one
+ * call gives.  Layouts, the words @64 / @68 / @124, IB's zero for an empty fragment, the NONE rows and the Quadrics
+ * classes (inline up to 52 bytes at +72, longer fragments at +128, slot_stride == 128 a bare envelope queue:
+ * checksummed only, with NONE not checksummed) are the send step's tables above.
+ * In each slot the header (72 or 128 bytes) and the payload bytes are written, and no other byte of the ring.
+ * h_ring and slot_stride need no alignment.  h_ring must not overlap h_msg.
+ * hipErrorInvalidValue: lampi_host_msg_bcopy's rules (frag_len 0 or above 1 GiB, a fragment range outside the
+ * message, NULL h_msg with msg_len > 0, NULL h_ring), a NULL h_fill, hdr_kind 2 or unknown, a mode other than the
+ * three, slot_stride below header + frag_len (except Quadrics' 128).  k_count == 0 returns 0, nothing written. */
+int lampi_host_msg_send_pack(const void *h_msg, size_t msg_len, size_t frag_len, size_t k_first, size_t k_count,
+                             void *h_ring, size_t slot_stride, const lampi_send_hdr_fill *h_fill, int hdr_kind,
+                             int mode);
+
+/* One received fragment of the host receive step (40 bytes, little-endian): offset 0 hdr_off, 8 frag_off, 16 app,
+ * 24 app_len, 32 length, 36 reserved. */
+typedef struct lampi_host_recv_slot {
+    uint64_t hdr_off;   /* the header's offset in the ring, ANY byte alignment */
+    uint64_t frag_off;  /* the payload's offset in the ring (Quadrics, 0 < length <= 52: ignored, the payload is at
+                           hdr_off + 72) */
+    void    *app;       /* host address it is delivered to */
+    int64_t  app_len;   /* room left in the posted buffer at that offset; may be <= 0 */
+    uint32_t length;    /* bytes received, length_m; all of them are checksummed */
+    uint32_t reserved;  /* 0 */
+} lampi_host_recv_slot;
+
+/* Receive: the header test, CopyToApp and CheckData for a drained batch in a host NIC ring
+ * [h_ring, h_ring + ring_bytes), in one call and with no host decision in between.  Per fragment the results are
+ * exactly lampi_recv_unpack_batch's: h_copied[i] = LAMPI_RECV_HDR_BAD, LAMPI_RECV_DATA_BAD or lengthToCopy,
+ * h_csum[i] the calculated checksum (0 for a dropped fragment), both masks (ceil(n/32) words each) and both counts
+ * overwritten; the expected value is the header's own word @64; the length comes from the record.
+ * A fragment whose header fails is dropped: it is not checksummed and NO application byte is written.  One
+ * relaxation of the device form's "no payload byte is read": the ring is one readable range (as for
+ * lampi_host_copy_to_app_batch), the DMA engines move a chunk's headers and payloads to the GPU together, so a
+ * dropped fragment's ring bytes may still cross PCIe; no kernel reads them.
+ * LAMPI_CSUM_NONE: no header is read or tested and only the lengthToCopy bytes are read.
+ * The CPU reads the slot records and no ring byte; headers are tested on the GPU at whatever alignment they have.
+ * hipErrorInvalidValue: NULL h_ring or h_slots with n > 0; any NULL output, even with n == 0; a nonzero reserved; a
+ * header range (every mode) or a payload range (lengthToCopy > 0, not inline) outside [0, ring_bytes); a NULL app
+ * with lengthToCopy > 0; a length above 1 GiB; n >= 2^32; a bad hdr_kind or mode.  n == 0 returns 0 with both
+ * counts zeroed.  The application buffers must not overlap the ring. */
+int lampi_host_recv_unpack_batch(const void *h_ring, size_t ring_bytes, const lampi_host_recv_slot *h_slots, size_t n,
+                                 int hdr_kind, int64_t *h_copied, uint32_t *h_csum, uint32_t *h_hdr_mask,
+                                 uint32_t *h_data_mask, uint32_t *h_nbad /* 2 words */, int mode);
+
+/* ------------------------------------------------------------------------------------
  * Typemap forms of the one-call send and receive steps: the non-contiguous datatype branch of
  * gmSendFragDesc::init (ref src/path/gm/sendFrag.cc:157-217, src/path/ib/sendFrag.cc:140-203) and of
  * RecvDesc_t::CopyToApp (src/path/common/BaseDesc.cc:72-163, 326-340) without per-piece descriptors.  They mirror

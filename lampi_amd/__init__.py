@@ -9,6 +9,7 @@ kernels for gfx950 behind the C ABI in include/lampi_csum.h (liblampi_csum.so).
   ``uicsum``, ``bcopy_uicsum``, ``header_checksum``), computed on the GPU.
 * :mod:`lampi_amd.device` -- batched device-resident checksums over torch tensors
   (imported lazily: it needs torch).
+* :mod:`lampi_amd.host` -- the one-call send and receive steps over numpy arrays in host memory.
 """
 from ._lib import (CRC32, CRC_INITIAL_REGISTER, CRC_POLYNOMIAL, HDR_GM, HDR_IB, HDR_QUADRICS, NONE,  # noqa: F401
                    RECV_DATA_BAD, RECV_HDR_BAD, SUM32, FragDesc, lib)

@@ -76,6 +76,17 @@ class HostPiece(ctypes.Structure):
 
 assert ctypes.sizeof(HostPiece) == 32
 
+
+class HostRecvSlot(ctypes.Structure):
+    """struct lampi_host_recv_slot (40 bytes): hdr_off u64, frag_off u64, app ptr, app_len i64, length u32,
+    reserved u32."""
+
+    _fields_ = [("hdr_off", ctypes.c_uint64), ("frag_off", ctypes.c_uint64), ("app", ctypes.c_void_p),
+                ("app_len", ctypes.c_int64), ("length", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(HostRecvSlot) == 40
+
 HDR_GM = 0  # enum lampi_send_hdr_kind (include/lampi_csum.h)
 HDR_IB = 1
 HDR_QUADRICS = 3  # the 128-byte quadricsCtlHdr_t (2 is not a kind)
@@ -218,6 +229,10 @@ PROTOTYPES = {
     "lampi_host_chain_csum_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.c_int]),
     "lampi_host_chain_copy_to_app_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p,
                                                           c_void_p, c_void_p, c_void_p, ctypes.c_int]),
+    "lampi_host_msg_send_pack": (ctypes.c_int, [c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t,
+                                                c_void_p, ctypes.c_int, ctypes.c_int]),
+    "lampi_host_recv_unpack_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_int, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int]),
     "lampi_device_scratch_bytes": (ctypes.c_int64, []),
     "lampi_host_register": (ctypes.c_int, [c_void_p, c_size_t]),
     "lampi_host_unregister": (ctypes.c_int, [c_void_p]),

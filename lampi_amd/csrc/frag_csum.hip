@@ -6211,6 +6211,56 @@ __global__ void __launch_bounds__(256) qrecv_hdr_test_kernel(const uint8_t *__re
     rec[i] = RecvHdrRec{ok ? 1u : 0u, w[16]};
 }
 
+// The header pre-pass of the host receive step (host_pack.cc: lampi_host_recv_unpack_batch).  A chunk of a host NIC
+// ring arrives in a staging buffer as the DMA runs left it, so header f sits at its own address hdr_addr[f] of ANY
+// byte alignment: kWords + 1 aligned words (the last only when the address is off the word grid, so nothing past
+// the header's last word is read) joined by a funnel shift.  One thread per fragment tests it as
+// recv_hdr_test_kernel / qrecv_hdr_test_kernel do and prepares the fragment's descriptor for the unchanged
+// launch_copy_to_app that follows on the stream: the word @64 goes into the descriptor's reserved word (where that
+// launch reads the expected checksum), a failed header zeroes app_len (nothing read, copied or checksummed for it),
+// and a Quadrics payload of 1..52 bytes is read from its header at +72.  bad[f] = 1 when the header fails.
+template <bool kQuadrics>
+__global__ void __launch_bounds__(256) host_recv_hdr_kernel(lampi_recv_desc *__restrict__ d,
+                                                            const uint64_t *__restrict__ hdr_addr, uint32_t n, int kind,
+                                                            int mode, const uint32_t *__restrict__ img,
+                                                            uint32_t *__restrict__ bad) {
+    __shared__ uint32_t S[1024];
+    if (mode == LAMPI_CSUM_CRC32) stage_slices(S, img);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    constexpr int kWords = kQuadrics ? (int)kQHdrWords : (int)kRecvHdrWords;
+    const uint64_t addr = hdr_addr[i];
+    const uint32_t sh = 8u * (uint32_t)(addr & 3u);
+    guint *a = (guint *)(uintptr_t)(addr & ~(uint64_t)3);
+    uint32_t raw[kWords + 1], w[kWords];
+#pragma unroll
+    for (int k = 0; k < kWords; ++k) raw[k] = a[k];
+    raw[kWords] = sh ? a[kWords] : 0u;
+#pragma unroll
+    for (int k = 0; k < kWords; ++k) w[k] = (uint32_t)((((uint64_t)raw[k + 1] << 32) | raw[k]) >> sh);
+    bool ok;
+    if constexpr (kQuadrics) {
+        const uint32_t c = q_hdr_csum(w, mode == LAMPI_CSUM_CRC32, SliceLds{S}), stored = w[kQHdrWords - 1];
+        ok = mode == LAMPI_CSUM_CRC32 ? c == stored : c + stored == stored + stored;
+    } else {
+        ok = recv_hdr_ok(w, kind, mode, SliceLds{S});
+    }
+    bad[i] = ok ? 0u : 1u;
+    gwuint *dw = (gwuint *)(d + i);  // words: frag 0-1, app 2-3, app_len 4-5, length 6, reserved 7
+    dw[7] = w[kSendDataCsum / 4];
+    if (!ok) {
+        dw[4] = 0u;
+        dw[5] = 0u;
+    } else if (kQuadrics) {
+        const uint32_t len = ((guint *)(d + i))[6];
+        if (len != 0u && len <= kQInline) {
+            const uint64_t p = addr + kQData;
+            dw[0] = (uint32_t)p;
+            dw[1] = (uint32_t)(p >> 32);
+        }
+    }
+}
+
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) u32x2 gwu32x2;
 
@@ -6978,6 +7028,15 @@ hipError_t launch_msg_send_pack(const uint8_t *base, size_t msg_len, size_t frag
         e = launch_per_item(send_stamp_kernel<true>, n, s, ring, slot_stride, (uint32_t)n, (const uint32_t *)vals,
                             (const lampi_copy_desc *)nullptr, f, msg_len, frag_len, kind, mode, img);
     return e;
+}
+
+hipError_t launch_host_recv_hdr(lampi_recv_desc *d, const uint64_t *hdr_addr, size_t n, int kind, int mode,
+                                const uint32_t *img, uint32_t *bad, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (!img || mode == LAMPI_CSUM_NONE) return hipErrorInvalidValue;  // (checksumming off tests no header)
+    if (kind == LAMPI_SEND_HDR_QUADRICS)
+        return launch_per_item(host_recv_hdr_kernel<true>, n, s, d, hdr_addr, (uint32_t)n, kind, mode, img, bad);
+    return launch_per_item(host_recv_hdr_kernel<false>, n, s, d, hdr_addr, (uint32_t)n, kind, mode, img, bad);
 }
 
 // ---- the typemap forms of both steps (lampi_tmap_send_pack / lampi_tmap_recv_unpack) -----------------------

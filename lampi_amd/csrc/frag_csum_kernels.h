@@ -95,6 +95,12 @@ hipError_t launch_recv_unpack(const lampi_recv_desc *d, size_t n, const uint8_t 
 hipError_t launch_msg_recv_unpack(const uint8_t *ring, size_t nslots, size_t slot_stride, int kind, uint8_t *app,
                                   size_t app_len, uint64_t seq0, int64_t *copied, uint32_t *csum, uint32_t *hmask,
                                   uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img, hipStream_t s);
+// The header pre-pass of the host receive step (host_pack.cc): header f, the 72 (Quadrics: 128) bytes at the device
+// address hdr_addr[f] of any byte alignment, is tested as launch_recv_unpack tests it (mode CRC32 or SUM32);
+// bad[f] = 1 when it fails.  It prepares d[f] for launch_copy_to_app on the same stream: reserved = the word @64,
+// app_len = 0 for a failed header, frag = the header + 72 for a Quadrics payload of 1..52 bytes.
+hipError_t launch_host_recv_hdr(lampi_recv_desc *d, const uint64_t *hdr_addr, size_t n, int kind, int mode,
+                                const uint32_t *img, uint32_t *bad, hipStream_t s);
 // Both steps through a datatype's typemap (tmap_kernels.h): one 4 KiB row of a fragment's packed bytes per wave,
 // gathered from / scattered to the typemap's pieces of base, checksummed from the registers that hold it; the
 // headers built and stamped (send) or tested first and the verdicts given last (receive) as the ring forms do.

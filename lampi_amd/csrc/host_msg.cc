@@ -56,7 +56,7 @@ struct PipeCtx {
             if (d) (void)hipFree(d);
         pinned_free(p.hmeta, p.hmeta_cap);
         for (int b = 0; b < kBufs; ++b)
-            for (hipEvent_t e : {p.in_done[b], p.k_done[b], p.out_done[b]})
+            for (hipEvent_t e : {p.in_done[b], p.k_done[b], p.out_done[b], p.v_done[b]})
                 if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {p.s_in, p.s_k, p.s_out})
             if (s) (void)hipStreamDestroy(s);
@@ -93,7 +93,7 @@ hipError_t pipe_ctx(PipeState **out) {
         p.dev = dev;
         for (hipStream_t *s : {&p.s_in, &p.s_k, &p.s_out}) TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
         for (int b = 0; b < kBufs; ++b)
-            for (hipEvent_t *e : {&p.in_done[b], &p.k_done[b], &p.out_done[b]})
+            for (hipEvent_t *e : {&p.in_done[b], &p.k_done[b], &p.out_done[b], &p.v_done[b]})
                 TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     *out = &p;

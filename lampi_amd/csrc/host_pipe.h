@@ -1,6 +1,7 @@
 // host_pipe.h -- the per-thread H2D || kernel || D2H pipeline behind the host-memory paths of
 // liblampi_csum.so (internal): the send side (host_msg.cc: lampi_host_msg_csum / _bcopy) and the
-// receive side (host_recv.cc: lampi_host_copy_to_app_batch, the host header checks).
+// receive side (host_recv.cc: lampi_host_copy_to_app_batch, the host header checks) and the one-call steps over
+// both (host_pack.cc: lampi_host_msg_send_pack, lampi_host_recv_unpack_batch).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,7 @@ struct PipeState {
     int dev = -1;
     hipStream_t s_in = nullptr, s_k = nullptr, s_out = nullptr;
     hipEvent_t in_done[kBufs] = {}, k_done[kBufs] = {}, out_done[kBufs] = {};
+    hipEvent_t v_done[kBufs] = {};  // a chunk's header verdicts are in pinned memory (host_pack.cc)
     uint8_t *dchunk = nullptr;  // kBufs input chunks of chunk_bytes
     size_t chunk_bytes = 0;
     uint8_t *dout = nullptr;  // kBufs output chunks of out_bytes (receive: the app-bound bytes)
