@@ -763,7 +763,8 @@ typedef struct lampi_tmap {          /* HOST memory, read during the call; 40 by
  * reserved, count * packed_size >= 2^63, pack_off + pack_len > count * packed_size, more than 2^32 - 1 fragments,
  * any bit in mode beyond the three modes (no hint, no LAMPI_CSUM_BY_BYTES), hdr_kind other than GM or IB.
  * LAMPI_SEND_HDR_QUADRICS is refused: its inline payloads are placed by a pass that reads a contiguous message;
- * gathered inline payloads are not built yet.
+ * gathered inline payloads are not built for device memory; for a datatype in host memory
+ * lampi_host_tmap_send_pack / lampi_host_tmap_recv_unpack_batch below serve all three kinds.
  * One 4 KiB row of the packed bytes per wave, each byte loaded once from its piece and stored once; scratch is a
  * word per row from the stream's pooled buffers (the call may be captured into a graph). */
 int lampi_tmap_send_pack(const void *d_base, const lampi_tmap *h_tmap, uint64_t pack_off, uint64_t pack_len,
@@ -859,6 +860,62 @@ int lampi_tmap_recv_unpack_batch(const lampi_tmap_frag *d_frags, size_t n, const
                                  uint32_t max_len, const void *d_hdrs, size_t hdr_stride, int hdr_kind,
                                  int64_t *d_copied, uint32_t *d_csum, uint32_t *d_hdr_mask, uint32_t *d_data_mask,
                                  uint32_t *d_nbad /* 2 words */, int mode, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Host-memory forms of the typemap steps: the non-contiguous datatype branch for a message, an application buffer
+ * and a NIC ring in HOST memory (page-locked or pageable).  They are to lampi_tmap_send_pack /
+ * lampi_tmap_recv_unpack_batch what the host-memory forms of the one-call steps are to the ring forms: synchronous,
+ * on the calling thread's own streams, chunked; they return 0 or a hipError_t, and invalid arguments return
+ * hipErrorInvalidValue before anything is written.  The DMA engines gather and scatter the pieces (one pitched
+ * transfer per typemap pair over a chunk's whole elements), the kernels see packed bytes -- so all three header
+ * kinds are served, LAMPI_SEND_HDR_QUADRICS included, in all three modes.  The address rule is the one above with
+ * h_base in place of d_base.
+ * ---------------------------------------------------------------------------------- */
+
+typedef struct lampi_host_tmap {     /* HOST memory, 40 bytes: lampi_tmap with the pairs in host memory */
+    const lampi_tmap_elt *h_pairs;   /* dtype->type_map itself, num_pairs entries, read during the call */
+    uint64_t extent, packed_size, count;
+    uint32_t num_pairs, reserved;    /* reserved = 0 */
+} lampi_host_tmap;
+
+/* Send.  The ring is, byte for byte, what lampi_host_msg_send_pack leaves for h_msg = the packed bytes
+ * [pack_off, pack_off + pack_len) of the message, k_first = 0 and every fragment: h_fill's series are indexed by the
+ * fragment j of the window, as in lampi_tmap_send_pack; pack_len == 0 gives one empty fragment whose header is still
+ * written.  GM, IB and Quadrics (inline at +72, longer payloads at +128, slot_stride == 128 the bare queue), CRC32,
+ * SUM32 and NONE.  No other ring byte is written, h_base is only read -- the pieces' bytes, or, for a fine-grained
+ * type whose gaps are all under 4096 bytes, bytes on pages that a piece of the window's elements touches.  h_ring
+ * and slot_stride need no alignment.
+ * hipErrorInvalidValue: lampi_host_msg_send_pack's rules (hdr_kind 2 or unknown, a mode other than the three,
+ * frag_len 0 or above 1 GiB, slot_stride below header + frag_len except Quadrics' 128, NULL h_ring or h_fill);
+ * lampi_tmap_send_pack's (NULL h_tmap or h_pairs, num_pairs == 0, packed_size == 0, a nonzero reserved,
+ * count * packed_size >= 2^63, a window past the message, more than 2^32 - 1 fragments); and, the pairs being in
+ * host memory, an inconsistent typemap: seq_offset[0] != 0, seq_offset[i+1] != seq_offset[i] + size[i], a size of
+ * 0, sizes that do not sum to packed_size. */
+int lampi_host_tmap_send_pack(const void *h_base, const lampi_host_tmap *h_tmap, uint64_t pack_off,
+                              uint64_t pack_len, size_t frag_len, void *h_ring, size_t slot_stride,
+                              const lampi_send_hdr_fill *h_fill, int hdr_kind, int mode);
+
+typedef struct lampi_host_tmap_slot { /* 32 bytes */
+    uint64_t hdr_off;    /* header's offset in the ring, any byte alignment */
+    uint64_t frag_off;   /* payload's offset in the ring (Quadrics, 0 < length <= 52: ignored) */
+    uint64_t pack_off;   /* first packed byte of the fragment: dataSeqOffset - seq_offset0, by the caller */
+    uint32_t length, reserved;
+} lampi_host_tmap_slot;
+
+/* Receive.  The five outputs equal lampi_host_recv_unpack_batch's for the same headers and payloads with
+ * app_len_i = count * packed_size - pack_off_i (0 when pack_off_i is at or past the end); the lengthToCopy bytes of
+ * each fragment that passed are scattered to their pieces of h_base.  A fragment whose header fails is dropped and
+ * writes nothing; bytes between the pieces and past `count` elements are never written (truncation as in
+ * lampi_tmap_recv_unpack); where two deliveries overlap those bytes are unspecified.  LAMPI_CSUM_NONE reads no
+ * header.  One typemap serves the whole call.
+ * hipErrorInvalidValue: lampi_host_recv_unpack_batch's rules (hdr_kind, mode, NULL h_ring or h_slots with n > 0,
+ * any NULL output even with n == 0, a nonzero reserved, a header or -- lengthToCopy > 0, not inline -- payload range
+ * outside the ring, a length above 1 GiB, n >= 2^32) and the typemap rules of the send form.  n == 0 returns 0 with
+ * both counts zeroed. */
+int lampi_host_tmap_recv_unpack_batch(const void *h_ring, size_t ring_bytes, const lampi_host_tmap_slot *h_slots,
+                                      size_t n, int hdr_kind, void *h_base, const lampi_host_tmap *h_tmap,
+                                      int64_t *h_copied, uint32_t *h_csum, uint32_t *h_hdr_mask,
+                                      uint32_t *h_data_mask, uint32_t *h_nbad /* 2 words */, int mode);
 
 /* ------------------------------------------------------------------------------------
  * Utilities (bench/test support, device-side).

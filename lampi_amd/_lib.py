@@ -144,6 +144,26 @@ class TmapFrag(ctypes.Structure):
 
 assert ctypes.sizeof(TmapFrag) == 32
 
+
+class HostTmap(ctypes.Structure):
+    """struct lampi_host_tmap (40 bytes, host): lampi_tmap with the pairs in host memory (h_pairs)."""
+
+    _fields_ = [("h_pairs", ctypes.c_void_p), ("extent", ctypes.c_uint64), ("packed_size", ctypes.c_uint64),
+                ("count", ctypes.c_uint64), ("num_pairs", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(HostTmap) == 40
+
+
+class HostTmapSlot(ctypes.Structure):
+    """struct lampi_host_tmap_slot (32 bytes): hdr_off, frag_off, pack_off u64, length, reserved u32."""
+
+    _fields_ = [("hdr_off", ctypes.c_uint64), ("frag_off", ctypes.c_uint64), ("pack_off", ctypes.c_uint64),
+                ("length", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(HostTmapSlot) == 32
+
 _lock = threading.Lock()
 _lib = None
 
@@ -233,6 +253,11 @@ PROTOTYPES = {
                                                 c_void_p, ctypes.c_int, ctypes.c_int]),
     "lampi_host_recv_unpack_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_int, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int]),
+    "lampi_host_tmap_send_pack": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint64, c_size_t,
+                                                 c_void_p, c_size_t, c_void_p, ctypes.c_int, ctypes.c_int]),
+    "lampi_host_tmap_recv_unpack_batch": (ctypes.c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.c_int,
+                                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                         c_void_p, ctypes.c_int]),
     "lampi_device_scratch_bytes": (ctypes.c_int64, []),
     "lampi_host_register": (ctypes.c_int, [c_void_p, c_size_t]),
     "lampi_host_unregister": (ctypes.c_int, [c_void_p]),

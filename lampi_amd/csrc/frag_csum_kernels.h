@@ -112,6 +112,9 @@ hipError_t launch_tmap_recv_unpack(const uint8_t *ring, size_t nslots, size_t sl
                                    const lampi_tmap &tm, uint64_t seq0, int64_t *copied, uint32_t *csum,
                                    uint32_t *hmask, uint32_t *dmask, uint32_t *nbad, int mode, const uint32_t *img,
                                    hipStream_t s);
+// The send step's copy-only rows alone: packed bytes [pack_off, pack_off + pack_len) gathered to dst (host_tmap.cc).
+hipError_t launch_tmap_gather(const uint8_t *base, const lampi_tmap &tm, uint64_t pack_off, uint64_t pack_len,
+                              uint8_t *dst, hipStream_t s);
 // ... over fragment records and a message table (both device memory): every fragment its own payload, window and
 // message; a frame of max(1, ceil(max_len / 4096)) rows for all of them; invalid records are skipped (send) or
 // dropped (receive) on the device.  hdrs: the caller's headers (send: null with GM and checksumming off; receive:

@@ -67,8 +67,11 @@ lampi_send_hdr_fill shifted_fill(const lampi_send_hdr_fill &f, size_t k, size_t 
     return g;
 }
 
+}  // namespace
+
 hipError_t host_send_pack(const uint8_t *h_msg, size_t msg_len, size_t frag_len, size_t k_first, size_t k_count,
-                          uint8_t *h_ring, size_t stride, const lampi_send_hdr_fill &fill, int kind, int mode) {
+                          uint8_t *h_ring, size_t stride, const lampi_send_hdr_fill &fill, int kind, int mode,
+                          const SendSource *src) {
     PipeState *pp = nullptr;
     TRY(pipe_ctx(&pp));
     PipeState &p = *pp;
@@ -83,7 +86,8 @@ hipError_t host_send_pack(const uint8_t *h_msg, size_t msg_len, size_t frag_len,
     const size_t width = sh.row(frag_len);                      // bytes of a full fragment's slot
     const size_t dstride = align_up(width, 8);                  // slots of the device image
     const size_t fpc = std::max<size_t>(1, chunk_target(true) / frag_len);  // fragments per chunk
-    TRY(ensure_chunks(p, fpc * frag_len));
+    const size_t stage_off = align_up(fpc * frag_len, 256);  // (a source's staging bytes, behind the chunk's own)
+    TRY(ensure_chunks(p, src ? stage_off + src->extra : fpc * frag_len));
     TRY(ensure_out_chunks(p, fpc * dstride));
 
     PipeDrain drain(p);  // any early return below leaves nothing in flight
@@ -99,9 +103,13 @@ hipError_t host_send_pack(const uint8_t *h_msg, size_t msg_len, size_t frag_len,
             TRY(hipStreamWaitEvent(p.s_in, p.k_done[b], 0));
             TRY(hipStreamWaitEvent(p.s_k, p.out_done[b], 0));
         }
-        if (nb) TRY(hipMemcpyAsync(d, h_msg + off, nb, hipMemcpyHostToDevice, p.s_in));
+        if (nb && src)
+            TRY(src->in(src->ctx, off, nb, d, d + stage_off, p.s_in));
+        else if (nb)
+            TRY(hipMemcpyAsync(d, h_msg + off, nb, hipMemcpyHostToDevice, p.s_in));
         TRY(hipEventRecord(p.in_done[b], p.s_in));
         TRY(hipStreamWaitEvent(p.s_k, p.in_done[b], 0));
+        if (nb && src && src->gather) TRY(src->gather(src->ctx, off, nb, d, d + stage_off, p.s_k));
         const lampi_send_hdr_fill g = shifted_fill(fill, k_first + f0, frag_len, quadrics);
         TRY(launch_msg_send_pack(d, nb, frag_len, dimg, dstride, g, nf, kind, mode, img, p.s_k));
         TRY(hipEventRecord(p.k_done[b], p.s_k));
@@ -124,6 +132,8 @@ hipError_t host_send_pack(const uint8_t *h_msg, size_t msg_len, size_t frag_len,
     return hipSuccess;
 }
 
+namespace {
+
 // ---- receive ------------------------------------------------------------------------------------------
 
 // Per-thread planning scratch, kept between calls.
@@ -142,9 +152,11 @@ struct Pending {
     const std::vector<OutXfer> *out = nullptr;
 };
 
+}  // namespace
+
 hipError_t host_recv_unpack(const uint8_t *h_ring, size_t ring_bytes, const lampi_host_recv_slot *f, size_t n,
                             int kind, int64_t *h_copied, uint32_t *h_csum, uint32_t *h_hmask, uint32_t *h_dmask,
-                            uint32_t *h_nbad, int mode) {
+                            uint32_t *h_nbad, int mode, const OutSink *sink) {
     UnpackScratch &us = t_unpack;
     if (us.din.size() < 2 * n) {
         us.din.resize(2 * n);
@@ -189,7 +201,13 @@ hipError_t host_recv_unpack(const uint8_t *h_ring, size_t ring_bytes, const lamp
         TRY(hipEventSynchronize(p.v_done[q.b]));
         for (size_t j = q.f0; j < q.f1 && !dropped; ++j) dropped = hbad[j] != 0;
         TRY(hipStreamWaitEvent(p.s_out, p.k_done[q.b], 0));
-        if (!dropped) {
+        const auto put = [&](uint8_t *h, const uint8_t *d, size_t len) -> hipError_t {
+            return sink ? sink->run(sink->ctx, h, d, len, p.s_out)
+                        : hipMemcpyAsync(h, d, len, hipMemcpyDeviceToHost, p.s_out);
+        };
+        if (!dropped && sink) {
+            TRY(issue_out_rows(*q.out, dout, put));
+        } else if (!dropped) {
             TRY(issue_out(*q.out, dout, p.s_out));
         } else {
             uint8_t *h = nullptr;
@@ -201,7 +219,7 @@ hipError_t host_recv_unpack(const uint8_t *h_ring, size_t ring_bytes, const lamp
                     continue;
                 }
                 if (j < q.f1 && !c) continue;  // dropped, or nothing to deliver: the open run stays open
-                if (len) TRY(hipMemcpyAsync(h, dout + doff, len, hipMemcpyDeviceToHost, p.s_out));
+                if (len) TRY(put(h, dout + doff, len));
                 h = c ? (uint8_t *)f[j].app : nullptr;
                 doff = c ? us.dout[items.data_item(j)] : 0;
                 len = c;
@@ -298,7 +316,6 @@ hipError_t host_recv_unpack(const uint8_t *h_ring, size_t ring_bytes, const lamp
     return hipSuccess;
 }
 
-}  // namespace
 }  // namespace lampi
 
 using namespace lampi;

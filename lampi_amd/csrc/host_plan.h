@@ -382,5 +382,15 @@ inline hipError_t issue_out(const std::vector<OutXfer> &v, const uint8_t *dout, 
     }
     return hipSuccess;
 }
+// ... or hand every row of them to run(h, d, len) instead (an OutSink, host_internal.h).
+template <class Run>
+inline hipError_t issue_out_rows(const std::vector<OutXfer> &v, const uint8_t *dout, Run run) {
+    for (const OutXfer &t : v)
+        for (size_t r = 0; r < t.rows; ++r) {
+            const hipError_t e = run(t.h + r * t.hpitch, dout + t.doff + r * t.dpitch, t.width);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
 
 }  // namespace lampi

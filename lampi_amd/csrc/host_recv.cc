@@ -85,9 +85,11 @@ struct RecvScratch {
 };
 thread_local RecvScratch t_recv;
 
+}  // namespace
+
 hipError_t host_recv(const uint8_t *h_ring, size_t ring_bytes, const lampi_host_recv_frag *f, size_t n,
                      int64_t *h_copied, uint32_t *h_csum, uint32_t *h_mask, uint32_t *h_nbad, int mode,
-                     uint32_t hint_override) {
+                     uint32_t hint_override, const OutSink *sink) {
     RecvScratch &rs = t_recv;
     if (rs.din.size() < n) {
         rs.din.resize(n);
@@ -150,7 +152,12 @@ hipError_t host_recv(const uint8_t *h_ring, size_t ring_bytes, const lampi_host_
                                (uint32_t *)(dm + o_csum) + f0, dmask, dnbad, mode, img, p.s_k, hint));
         TRY(hipEventRecord(p.k_done[b], p.s_k));
         TRY(hipStreamWaitEvent(p.s_out, p.k_done[b], 0));
-        TRY(issue_out(rs.out, dout, p.s_out));
+        if (sink)
+            TRY(issue_out_rows(rs.out, dout, [&](uint8_t *h, const uint8_t *d, size_t len) {
+                return sink->run(sink->ctx, h, d, len, p.s_out);
+            }));
+        else
+            TRY(issue_out(rs.out, dout, p.s_out));
         TRY(hipEventRecord(p.out_done[b], p.s_out));
     }
     TRY(hipMemcpyAsync(p.hmeta + o_copied, dm + o_copied, o_scratch - o_copied, hipMemcpyDeviceToHost, p.s_k));
@@ -171,6 +178,8 @@ hipError_t host_recv(const uint8_t *h_ring, size_t ring_bytes, const lampi_host_
     *h_nbad = nbad;
     return hipSuccess;
 }
+
+namespace {
 
 // The header checks of a batch of received fragments: each header's first `need` bytes are gathered
 // from the ring into pinned records (the CPU moves header bytes only), checked on the device a chunk

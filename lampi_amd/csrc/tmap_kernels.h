@@ -671,6 +671,19 @@ hipError_t launch_tmap_send_pack(const uint8_t *base, const lampi_tmap &tm, uint
     return e;
 }
 
+// Packed bytes [pack_off, pack_off + pack_len) gathered to dst, nothing else: the copy-only rows of the send step
+// over one-row fragments 4096 bytes apart (no header is written, no value kept).  For the host typemap form's span
+// route (host_tmap.cc), whose base is a staged copy of the elements' footprints.
+hipError_t launch_tmap_gather(const uint8_t *base, const lampi_tmap &tm, uint64_t pack_off, uint64_t pack_len,
+                              uint8_t *dst, hipStream_t s) {
+    if (pack_len == 0) return hipSuccess;
+    TmapJob J = tmap_job(tm, const_cast<uint8_t *>(base), dst - kSendHdrBytes, kRowBytes, kRowBytes, nullptr);
+    J.pack_off = pack_off;
+    J.pack_len = pack_len;
+    J.frag_len = (uint32_t)kRowBytes;
+    return launch_tmap_rows<false>(J, (size_t)((pack_len + kRowBytes - 1) / kRowBytes), nullptr, LAMPI_CSUM_NONE, s);
+}
+
 // The receive step through a typemap (lampi_tmap_recv_unpack): the verdicts zeroed, recv_hdr_test_kernel over the
 // slots (max_len = slot_stride - 72; in every mode -- it tests the length), the rows of the slots that passed --
 // scattered through the typemap, cut at app_len = count * packed_size --, their join, and one verdict launch.
