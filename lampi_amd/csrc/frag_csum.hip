@@ -70,6 +70,52 @@ static hipError_t launch_per_item(Kernel kernel, size_t n, hipStream_t s, Args..
     return hipGetLastError();
 }
 
+// A main launch that lists the items it leaves to a second kernel, then that leftover launch (kLeftoverWgs
+// workgroups), over list_words words of the stream's scratch and its counter pair: main(list, left) counts the listed
+// items in *left; leftover(list, left, next_left) takes them and zeroes *next_left, where the stream's next call
+// counts.  Each callable launches one kernel and nothing else (the helper reads hipGetLastError after it).
+template <class Main, class Leftover>
+static hipError_t with_leftover_list(hipStream_t s, size_t list_words, Main &&main, Leftover &&leftover) {
+    uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
+    hipError_t e = stream_scratch(s, list_words * sizeof(uint32_t), (void **)&list);
+    if (e != hipSuccess) return e;
+    // the counter pair is taken only now (ADVICE r4): a failure before this point leaves it untouched
+    e = pair_counters(s, &left, &next_left);
+    if (e != hipSuccess) return e;
+    main(list, left);
+    e = hipGetLastError();
+    if (e == hipSuccess) {
+        leftover((const uint32_t *)list, (const uint32_t *)left, next_left);
+        e = hipGetLastError();
+    }
+    // a launch that failed left a counter unzeroed (the leftover kernel zeroes the next call's): zero both
+    if (e != hipSuccess) reset_pair_counters(s);
+    return e;
+}
+
+// Lanes of a join kernel per fragment of W row groups: the power of two up to min(W, 64).
+static uint32_t join_lanes(uint32_t W) {
+    uint32_t G = 1;
+    while (G < W && G < 64u) G <<= 1;
+    return G;
+}
+
+// A batch of n fragments as W > 1 row groups each (W clamped by the caller: light_groups, sum_groups): launch(items,
+// groups) fills one word per group over n * W items of the stream's scratch, then `join` -- (src, n, W, G, groups,
+// out), G lanes per fragment -- ends every fragment.
+template <class Src, class Launch, class Join>
+static hipError_t launch_groups_then_join(const Src &src, size_t n, uint32_t W, uint32_t *out, hipStream_t s,
+                                          Launch &&launch, Join join) {
+    uint32_t *groups = nullptr;
+    hipError_t e = stream_scratch(s, n * W * sizeof(uint32_t), (void **)&groups);
+    if (e != hipSuccess) return e;
+    launch(n * W, groups);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint32_t G = join_lanes(W);
+    return launch_per_item(join, n * G, s, src, n, W, G, groups, out);
+}
+
 namespace {
 
 constexpr uint32_t kLdsHorner = 65536;
@@ -3370,26 +3416,19 @@ constexpr unsigned kLeftoverWgs = 256;
 template <class Src>
 static hipError_t launch_crc_light_pair_copy(const Src &src, size_t n, const uint32_t *img, uint32_t *out,
                                              hipStream_t s, uint32_t *shape_nhalf) {
-    uint32_t *left = nullptr, *next_left = nullptr, *list = nullptr;
     constexpr int kWv = 8;  // waves per workgroup of the pair kernel
     const size_t nwg = (n + 2 * kWv - 1) / (2 * kWv);
     // (one entry per wave at most: a batch whose shape changed since the census leaves every wave)
-    hipError_t e = stream_scratch(s, nwg * kWv * sizeof(uint32_t), (void **)&list);
-    if (e != hipSuccess) return e;
-    // the counter pair is taken only now (ADVICE r4): a failure before this point leaves it untouched
-    e = pair_counters(s, &left, &next_left);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, kWv>), dim3((unsigned)nwg), dim3(64 * kWv), 0, s, src, n, img,
-                       out, left, list);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(crc_light_pair_leftover_kernel<Src>, dim3(kLeftoverWgs), dim3(256), 0, s, src, n, img, out,
-                           (const uint32_t *)left, next_left, (const uint32_t *)list, shape_nhalf);
-        e = hipGetLastError();
-    }
-    // a launch that failed left a counter unzeroed (the leftover kernel zeroes the next call's): zero both
-    if (e != hipSuccess) reset_pair_counters(s);
-    return e;
+    return with_leftover_list(
+        s, nwg * kWv,
+        [&](uint32_t *list, uint32_t *left) {
+            hipLaunchKernelGGL((crc_light_pair_copy_kernel<Src, kWv>), dim3((unsigned)nwg), dim3(64 * kWv), 0, s, src,
+                               n, img, out, left, list);
+        },
+        [&](const uint32_t *list, const uint32_t *left, uint32_t *next_left) {
+            hipLaunchKernelGGL(crc_light_pair_leftover_kernel<Src>, dim3(kLeftoverWgs), dim3(256), 0, s, src, n, img,
+                               out, left, next_left, list, shape_nhalf);
+        });
 }
 
 // waves per workgroup of the table-light copy kernels: four (the copy shape, four 36 KiB workgroups per CU).
@@ -3420,17 +3459,7 @@ static hipError_t launch_crc_light_frag_copy(const Src &src, size_t n, const uin
         launch(n, nullptr);
         return hipGetLastError();
     }
-    uint32_t *groups = nullptr;
-    hipError_t e = stream_scratch(s, n * W * sizeof(uint32_t), (void **)&groups);
-    if (e != hipSuccess) return e;
-    launch(n * W, groups);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-        uint32_t G = 1;
-        while (G < W && G < 64u) G <<= 1;
-        e = launch_per_item(crc_light_group_join_kernel<Src>, n * G, s, src, n, W, G, groups, out);
-    }
-    return e;
+    return launch_groups_then_join(src, n, W, out, s, launch, crc_light_group_join_kernel<Src>);
 }
 
 // ---- CRC fast path: regular batches -------------------------------------------------------
@@ -5614,7 +5643,21 @@ static void with_row4k_lanes(size_t L, Fn &&fn) {
         default: fn(std::integral_constant<int, 64>{}); break;
     }
 }
-static uint32_t pick_regular_fpw(size_t n, size_t span);
+
+// Read-kernel schedule, measured on MI355X (tools/microbench/crc_sweep.hip, profiles/r01_sweep.txt):
+// a workgroup covers ~384 KiB (fpw * span = 96 KiB per wave) and its waves walk fragments row by
+// row.  4 KiB fragments are visited in the order of 8 KiB ones (kV = 2: chain c reads two
+// consecutive fragments in turn): 81.4-82.4% of the HBM roofline at every batch offset measured
+// (0, 4 KiB .. 1.5 MiB) against 79.4-79.8% for the previous fpw = 32 fragment-order schedule and
+// 77-79% for the same 384 KiB in fragment order; the 16 KiB order (kV = 4, fpw 6) matched it
+// except at a 64 KiB batch offset (79.8%).  16 KiB fragments: fpw 6, 80.3-82.3% (fpw 12: 78.6%).
+// fpw stays even (two chains, no duplicate ring slots).
+static uint32_t pick_regular_fpw(size_t n, size_t span) {
+    uint32_t fpw = (uint32_t)std::max<size_t>(2, (96u * 1024u / span) & ~(size_t)1);
+    while (fpw > 1 && (size_t)kWaves * fpw * 512 > n) fpw >>= 1;  // small batches: more workgroups
+    return fpw;
+}
+
 static hipError_t launch_crc_desc_whole(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img,
                                         hipStream_t s, uint32_t R) {
     const size_t items = R == 1 ? n / 2 : n;  // pairs of 4 KiB fragments, or fragments
@@ -5622,30 +5665,55 @@ static hipError_t launch_crc_desc_whole(const lampi_frag_desc *d, size_t n, uint
     if (items > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const uint32_t fpw = pick_regular_fpw(items, span);
     if (fpw > (R == 1 ? 32u : 64u)) return hipErrorInvalidValue;  // (a wave's descriptors live in its 64 lanes)
-    uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
-    hipError_t e = stream_scratch(s, (items + 1) * sizeof(uint32_t), (void **)&list);
-    if (e != hipSuccess) return e;
-    e = pair_counters(s, &left, &next_left);
-    if (e != hipSuccess) return e;
-    if (R == 1)
-        hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, false, kWaves, 0, true>),
-                           grid_for(items, fpw), dim3(kBlock), 0, s, reinterpret_cast<const uint8_t *>(d),
-                           (uint32_t)items, fpw, span, 0u, img, out, nullptr, (size_t)0, list, left);
-    else
-        hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 1, false, kWaves, 0, true>),
-                           grid_for(items, fpw), dim3(kBlock), 0, s, reinterpret_cast<const uint8_t *>(d),
-                           (uint32_t)items, fpw, span, 0u, img, out, nullptr, (size_t)0, list, left);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(crc_light_pair_leftover_kernel<DescSource>, dim3(kLeftoverWgs), dim3(256), 0, s,
-                           DescSource{d}, n, img, out, (const uint32_t *)left, next_left, (const uint32_t *)list,
-                           (uint32_t *)nullptr);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) reset_pair_counters(s);
+    hipError_t e = with_leftover_list(
+        s, items + 1,
+        [&](uint32_t *list, uint32_t *left) {
+            if (R == 1)
+                hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, false, kWaves, 0, true>),
+                                   grid_for(items, fpw), dim3(kBlock), 0, s, reinterpret_cast<const uint8_t *>(d),
+                                   (uint32_t)items, fpw, span, 0u, img, out, nullptr, (size_t)0, list, left);
+            else
+                hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 1, false, kWaves, 0, true>),
+                                   grid_for(items, fpw), dim3(kBlock), 0, s, reinterpret_cast<const uint8_t *>(d),
+                                   (uint32_t)items, fpw, span, 0u, img, out, nullptr, (size_t)0, list, left);
+        },
+        [&](const uint32_t *list, const uint32_t *left, uint32_t *next_left) {
+            hipLaunchKernelGGL(crc_light_pair_leftover_kernel<DescSource>, dim3(kLeftoverWgs), dim3(256), 0, s,
+                               DescSource{d}, n, img, out, left, next_left, list, (uint32_t *)nullptr);
+        });
     if (e == hipSuccess && R == 1 && (n & 1u))
         e = launch_crc_light_frag_copy(DescSource{d + n - 1}, 1, img, out + n - 1, s);
     return e;
+}
+
+// Packed rows (crc_regular_kernel<kSub < 64>): 64 * kSub-byte fragments (kSub = 1 .. 32: 64 B .. 2 KiB) on config B's
+// schedule, 64 / kSub fragments per 4 KiB row, two rows per chain item (kV = 2), over nv whole 8 KiB items -- of a
+// message from base (16-byte aligned; d, list and left null), or of a descriptor batch from d[0].addr (base null; the
+// items holding anything else listed for the leftover launch).  The launch alone: the caller reads hipGetLastError.
+template <int kSub>
+static void launch_packed_k(const uint8_t *base, const lampi_frag_desc *d, size_t nv, uint32_t partial, uint32_t *out,
+                            const uint32_t *img, hipStream_t s, uint32_t *list, uint32_t *left) {
+    // (config B's choice, 12 items per wave; 1 GiB of 1 KiB fragments: 16 items 71.4%, 8 70.6%, 6 70.5-70.9%, 4 66%;
+    // a balanced grid of whole rounds of resident workgroups 68.6-71.1%, profiles/r06/packed_fpw.txt; a tapered grid
+    // ending on 512-2,048 workgroups of 2-6 items 68-72%, profiles/r06/packed_taper.txt)
+    const uint32_t fpw = pick_regular_fpw(nv, 2 * kRowBytes);
+    hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, false, kWaves, 0, false, kSub>),
+                       grid_for(nv, fpw), dim3(kBlock), 0, s, base, (uint32_t)nv, fpw, 2 * kRowBytes, partial, img, out,
+                       (uint8_t *)const_cast<lampi_frag_desc *>(d), (size_t)0, list, left);
+}
+// fn(std::integral_constant<int, kSub>) for a fragment length L of 64 B .. 2 KiB, a power of two.  Both callers test
+// that range before they come here -- launch_packed itself (any other length leaves *done at 0), launch_crc_desc for
+// launch_desc_packed (the census's contig_len) -- so the default is the 2 KiB case.
+template <class Fn>
+static void with_packed_sub(size_t L, Fn &&fn) {
+    switch (L) {
+        case 64: fn(std::integral_constant<int, 1>{}); break;
+        case 128: fn(std::integral_constant<int, 2>{}); break;
+        case 256: fn(std::integral_constant<int, 4>{}); break;
+        case 512: fn(std::integral_constant<int, 8>{}); break;
+        case 1024: fn(std::integral_constant<int, 16>{}); break;
+        default: fn(std::integral_constant<int, 32>{}); break;
+    }
 }
 
 // Read-only CRC descriptor batches the census saw as one contiguous run of equal L-byte fragments (L = 64 B .. 2 KiB,
@@ -5653,67 +5721,74 @@ static hipError_t launch_crc_desc_whole(const lampi_frag_desc *d, size_t n, uint
 // whole 8 KiB items from d[0].addr, each wave checking its items' descriptors first; items holding anything else are
 // listed by fragment pairs for crc_light_pair_leftover_kernel; the last fragments (past the whole items) on the
 // count split.
-template <int kSub>
-static hipError_t launch_packed_desc_k(const lampi_frag_desc *d, size_t nv, uint32_t *out, const uint32_t *img,
-                                       hipStream_t s, uint32_t *list, uint32_t *left) {
-    const uint32_t fpw = pick_regular_fpw(nv, 2 * kRowBytes);
-    hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, false, kWaves, 0, false, kSub>),
-                       grid_for(nv, fpw), dim3(kBlock), 0, s, (const uint8_t *)nullptr, (uint32_t)nv, fpw,
-                       2 * kRowBytes, 0u, img, out, (uint8_t *)const_cast<lampi_frag_desc *>(d), (size_t)0, list, left);
-    return hipGetLastError();
-}
 static hipError_t launch_desc_packed(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img,
                                      hipStream_t s, uint32_t L, size_t *done) {
     *done = 0;
     const size_t F = 2 * kRowBytes / L, nv = n / F;
     if (nv * 2 < kPackedMinRows || nv > 0xFFFFFFFFull || nv * F / 2 > 0xFFFFFFFFull) return hipSuccess;
-    uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
-    hipError_t e = stream_scratch(s, (nv * F / 2 + 1) * sizeof(uint32_t), (void **)&list);
-    if (e != hipSuccess) return e;
-    e = pair_counters(s, &left, &next_left);
-    if (e != hipSuccess) return e;
-    switch (L) {
-        case 64: e = launch_packed_desc_k<1>(d, nv, out, img, s, list, left); break;
-        case 128: e = launch_packed_desc_k<2>(d, nv, out, img, s, list, left); break;
-        case 256: e = launch_packed_desc_k<4>(d, nv, out, img, s, list, left); break;
-        case 512: e = launch_packed_desc_k<8>(d, nv, out, img, s, list, left); break;
-        case 1024: e = launch_packed_desc_k<16>(d, nv, out, img, s, list, left); break;
-        default: e = launch_packed_desc_k<32>(d, nv, out, img, s, list, left); break;
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(crc_light_pair_leftover_kernel<DescSource>, dim3(kLeftoverWgs), dim3(256), 0, s,
-                           DescSource{d}, nv * F, img, out, (const uint32_t *)left, next_left, (const uint32_t *)list,
-                           (uint32_t *)nullptr);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) reset_pair_counters(s);
+    const hipError_t e = with_leftover_list(
+        s, nv * F / 2 + 1,
+        [&](uint32_t *list, uint32_t *left) {
+            with_packed_sub(L, [&](auto kSub) {
+                launch_packed_k<decltype(kSub)::value>(nullptr, d, nv, 0u, out, img, s, list, left);
+            });
+        },
+        [&](const uint32_t *list, const uint32_t *left, uint32_t *next_left) {
+            hipLaunchKernelGGL(crc_light_pair_leftover_kernel<DescSource>, dim3(kLeftoverWgs), dim3(256), 0, s,
+                               DescSource{d}, nv * F, img, out, left, next_left, list, (uint32_t *)nullptr);
+        });
     if (e == hipSuccess) *done = nv * F;
     return e;
 }
 
-// SUM descriptor batches of equal 64 B .. 1 KiB fragments (the census saw one contiguous run): sum_row4k_desc_kernel
-// over the whole 4 KiB rows' worth of fragments (*done), the leftovers on sum_pair_leftover_kernel.
-static hipError_t launch_sum_desc_row4k(const lampi_frag_desc *d, size_t n, uint32_t *out, const uint32_t *img,
-                                        hipStream_t s, uint32_t L, size_t *done) {
+// The message form: fragments of 64 B .. 2 KiB (a power of two) at a 16-byte-aligned base.  Takes the first *done
+// fragments -- whole pairs of rows -- and leaves the rest (fewer than 128 / kSub plus the message's last, possibly
+// short, fragment) to the caller.
+static hipError_t launch_packed(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
+                                const uint32_t *img, hipStream_t s, size_t *done) {
+    *done = 0;
+    if (((uintptr_t)base & 15u) != 0 || frag_len < 64 || frag_len > kRowBytes / 2 || (frag_len & (frag_len - 1)) != 0)
+        return hipSuccess;
+    const size_t rows = msg_len / kRowBytes, nv = rows / 2;  // whole 8 KiB items: every fragment in them is full
+    if (rows < kPackedMinRows || nv > 0xFFFFFFFFull) return hipSuccess;
+    with_packed_sub(frag_len, [&](auto kSub) {
+        launch_packed_k<decltype(kSub)::value>(base, nullptr, nv, partial, out, img, s, nullptr, nullptr);
+    });
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) *done = nv * 2 * (kRowBytes / frag_len);
+    return e;
+}
+
+// SUM descriptor batches of equal 64 B .. 1 KiB fragments (the census saw one contiguous run), read-only (lampi_frag_desc:
+// sum_row4k_desc_kernel, the leftovers on sum_pair_leftover_kernel) or fused copies (lampi_copy_desc:
+// sum_row4k_copy_desc_kernel, sum_copy_list_kernel), over the whole 4 KiB rows' worth of fragments (*done).
+template <class Desc>
+static hipError_t launch_sum_desc_row4k(const Desc *d, size_t n, uint32_t *out, const uint32_t *img, hipStream_t s,
+                                        uint32_t L, size_t *done) {
+    constexpr bool kCopy = std::is_same<Desc, lampi_copy_desc>::value;
     *done = 0;
     const size_t F = kRowBytes / L, nrow = n / F;
     if (!row4k_rows(nrow) || nrow * F > 0xFFFFFFFFull) return hipSuccess;
-    uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
-    hipError_t e = stream_scratch(s, (nrow * F + 1) * sizeof(uint32_t), (void **)&list);
-    if (e != hipSuccess) return e;
-    e = pair_counters(s, &left, &next_left);
-    if (e != hipSuccess) return e;
-    with_row4k_lanes(L, [&](auto kG) {
-        hipLaunchKernelGGL(sum_row4k_desc_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0, s, d, img,
-                           out, list, left);
-    });
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(sum_pair_leftover_kernel, dim3(kLeftoverWgs), dim3(256), 0, s, d, nrow * F, out,
-                           (const uint32_t *)left, next_left, (const uint32_t *)list);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) reset_pair_counters(s);
+    const hipError_t e = with_leftover_list(
+        s, nrow * F + 1,
+        [&](uint32_t *list, uint32_t *left) {
+            with_row4k_lanes(L, [&](auto kG) {
+                if constexpr (kCopy)
+                    hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128),
+                                       0, s, d, img, out, list, left);
+                else
+                    hipLaunchKernelGGL(sum_row4k_desc_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0,
+                                       s, d, img, out, list, left);
+            });
+        },
+        [&](const uint32_t *list, const uint32_t *left, uint32_t *next_left) {
+            if constexpr (kCopy)
+                hipLaunchKernelGGL(sum_copy_list_kernel, dim3(kLeftoverWgs), dim3(128), 0, s, d, left, next_left, list,
+                                   out);
+            else
+                hipLaunchKernelGGL(sum_pair_leftover_kernel, dim3(kLeftoverWgs), dim3(256), 0, s, d, nrow * F, out,
+                                   left, next_left, list);
+        });
     if (e == hipSuccess) *done = nrow * F;
     return e;
 }
@@ -5845,9 +5920,6 @@ hipError_t launch_desc_per_wave(const lampi_frag_desc *d, size_t n, uint32_t *ou
     return hipGetLastError();
 }
 
-static hipError_t launch_packed(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
-                                const uint32_t *img, hipStream_t s, size_t *done);
-
 hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, size_t n,
                           uint32_t *out, const uint32_t *img, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -5863,10 +5935,10 @@ hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
     size_t done = 0;
     const hipError_t e = launch_packed(base, msg_len, frag_len, partial, out, img, s, &done);
     if (e != hipSuccess) return e;
-    if (done >= n) return hipSuccess;
     if (done)
-        return launch_crc_msg(base + done * frag_len, msg_len - done * frag_len, frag_len, partial, n - done,
-                              out + done, img, s);
+        return done >= n ? hipSuccess
+                         : launch_crc_msg(base + done * frag_len, msg_len - done * frag_len, frag_len, partial,
+                                          n - done, out + done, img, s);
     const size_t R = (frag_len + kRowBytes - 1) / kRowBytes;
     if (frag_len > 1024 && frag_len <= kRowBytes / 2 && (frag_len & 15u) != 0 && n >= kShapeMin &&
         pair_counters_ok(s))
@@ -5879,20 +5951,6 @@ hipError_t launch_crc_msg(const uint8_t *base, size_t msg_len, size_t frag_len, 
     hipLaunchKernelGGL((crc_stream_kernel<MsgSource, kStreamD, kStreamK, false, kStreamWv, kStreamCap>), frags_grid(n, fpg), dim3(64 * kStreamWv), 0, s,
                        MsgSource{base, msg_len, frag_len, partial}, n, fpg, img, out, nullptr);
     return hipGetLastError();
-}
-
-// Read-kernel schedule, measured on MI355X (tools/microbench/crc_sweep.hip, profiles/r01_sweep.txt):
-// a workgroup covers ~384 KiB (fpw * span = 96 KiB per wave) and its waves walk fragments row by
-// row.  4 KiB fragments are visited in the order of 8 KiB ones (kV = 2: chain c reads two
-// consecutive fragments in turn): 81.4-82.4% of the HBM roofline at every batch offset measured
-// (0, 4 KiB .. 1.5 MiB) against 79.4-79.8% for the previous fpw = 32 fragment-order schedule and
-// 77-79% for the same 384 KiB in fragment order; the 16 KiB order (kV = 4, fpw 6) matched it
-// except at a 64 KiB batch offset (79.8%).  16 KiB fragments: fpw 6, 80.3-82.3% (fpw 12: 78.6%).
-// fpw stays even (two chains, no duplicate ring slots).
-static uint32_t pick_regular_fpw(size_t n, size_t span) {
-    uint32_t fpw = (uint32_t)std::max<size_t>(2, (96u * 1024u / span) & ~(size_t)1);
-    while (fpw > 1 && (size_t)kWaves * fpw * 512 > n) fpw >>= 1;  // small batches: more workgroups
-    return fpw;
 }
 
 template <bool kSum>
@@ -5917,43 +5975,6 @@ static hipError_t launch_regular(const uint8_t *base, size_t n, size_t frag_len,
                        dim3(kBlock), 0, s, base + done * frag_len, (uint32_t)m, fpw, frag_len, partial, img, out + done,
                        nullptr, (size_t)0);
     return hipGetLastError();
-}
-
-// Packed rows (crc_regular_kernel<kSub < 64>): a message of 64 * kSub-byte fragments (kSub = 1 .. 32: 64 B ..
-// 2 KiB) at a 16-byte-aligned base on config B's schedule, 64 / kSub fragments per 4 KiB row, two rows per
-// chain item (kV = 2).  Takes the first *done fragments -- whole pairs of rows -- and leaves the rest (fewer
-// than 128 / kSub plus the message's last, possibly short, fragment) to the caller.
-template <int kSub>
-static hipError_t launch_packed_k(const uint8_t *base, size_t nv, uint32_t partial, uint32_t *out, const uint32_t *img,
-                                  hipStream_t s) {
-    // (config B's choice, 12 items per wave; 1 GiB of 1 KiB fragments: 16 items 71.4%, 8 70.6%, 6 70.5-70.9%, 4 66%;
-    // a balanced grid of whole rounds of resident workgroups 68.6-71.1%, profiles/r06/packed_fpw.txt; a tapered grid
-    // ending on 512-2,048 workgroups of 2-6 items 68-72%, profiles/r06/packed_taper.txt)
-    const uint32_t fpw = pick_regular_fpw(nv, 2 * kRowBytes);
-    hipLaunchKernelGGL((crc_regular_kernel<kRegularChains, false, false, 3, 2, false, kWaves, 0, false, kSub>),
-                       grid_for(nv, fpw), dim3(kBlock), 0, s, base, (uint32_t)nv, fpw, 2 * kRowBytes, partial, img, out,
-                       nullptr, (size_t)0);
-    return hipGetLastError();
-}
-static hipError_t launch_packed(const uint8_t *base, size_t msg_len, size_t frag_len, uint32_t partial, uint32_t *out,
-                                const uint32_t *img, hipStream_t s, size_t *done) {
-    *done = 0;
-    if (((uintptr_t)base & 15u) != 0 || frag_len < 64 || frag_len > kRowBytes / 2 || (frag_len & (frag_len - 1)) != 0)
-        return hipSuccess;
-    const size_t rows = msg_len / kRowBytes, nv = rows / 2;  // whole 8 KiB items: every fragment in them is full
-    if (rows < kPackedMinRows || nv > 0xFFFFFFFFull) return hipSuccess;
-    hipError_t e = hipErrorInvalidValue;
-    switch (frag_len) {
-        case 64: e = launch_packed_k<1>(base, nv, partial, out, img, s); break;
-        case 128: e = launch_packed_k<2>(base, nv, partial, out, img, s); break;
-        case 256: e = launch_packed_k<4>(base, nv, partial, out, img, s); break;
-        case 512: e = launch_packed_k<8>(base, nv, partial, out, img, s); break;
-        case 1024: e = launch_packed_k<16>(base, nv, partial, out, img, s); break;
-        case 2048: e = launch_packed_k<32>(base, nv, partial, out, img, s); break;
-        default: return hipSuccess;
-    }
-    if (e == hipSuccess) *done = nv * 2 * (kRowBytes / frag_len);
-    return e;
 }
 
 hipError_t launch_crc_regular(const uint8_t *base, size_t n, size_t frag_len, uint32_t partial, uint32_t *out,
@@ -6002,20 +6023,13 @@ static hipError_t launch_sum_copy_groups(const Src &src, size_t n, uint32_t *out
         launch_sum_copy(src, n, out, s, small);
         return hipGetLastError();
     }
-    uint32_t *groups = nullptr;
-    hipError_t e = stream_scratch(s, n * W * sizeof(uint32_t), (void **)&groups);
-    if (e != hipSuccess) return e;
     // (128 threads per group measured against 256 -- GM receive 72.5 -> 63% -- and a wave per group, four to a
     // workgroup -- 72.5 -> 62.4%)
     // (two or four groups per workgroup, grid-stride: GM receive 72.5 -> 71.2 / 69.6%)
-    launch_sum_copy(GroupSource<Src>{src, W}, n * W, groups, s);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-        uint32_t G = 1;
-        while (G < W && G < 64u) G <<= 1;
-        e = launch_per_item(sum_group_join_kernel<Src>, n * G, s, src, n, W, G, groups, out);
-    }
-    return e;
+    return launch_groups_then_join(
+        src, n, W, out, s,
+        [&](size_t items, uint32_t *groups) { launch_sum_copy(GroupSource<Src>{src, W}, items, groups, s); },
+        sum_group_join_kernel<Src>);
 }
 
 // SUM message copies of fragments of R rows: the row groups to run (1: sum_copy_row_kernel's row items).
@@ -6067,28 +6081,10 @@ hipError_t launch_bcopy_desc(const lampi_copy_desc *d, size_t n, uint32_t *out, 
     // the rest after them.  Same box, interleaved (profiles/r06/sum_row4k_cd_ab.txt), of read + write: 1 KiB 69.0 ->
     // 77.3%, 256 B 23.7 -> 77.7%, 64 B 6.9 -> 63.0% (to + 8 / + 1 destinations 58-74%).
     if (!crc && given <= 1 && row4k_len(contig)) {
-        const size_t F = kRowBytes / contig, nrow = n / F;
-        if (row4k_rows(nrow) && nrow * F <= 0xFFFFFFFFull) {
-            uint32_t *list = nullptr, *left = nullptr, *next_left = nullptr;
-            hipError_t e = stream_scratch(s, (nrow * F + 1) * sizeof(uint32_t), (void **)&list);
-            if (e != hipSuccess) return e;
-            e = pair_counters(s, &left, &next_left);
-            if (e != hipSuccess) return e;
-            with_row4k_lanes(contig, [&](auto kG) {
-                hipLaunchKernelGGL(sum_row4k_copy_desc_kernel<decltype(kG)::value>, dim3((unsigned)nrow), dim3(128), 0,
-                                   s, d, img, out, list, left);
-            });
-            e = hipGetLastError();
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(sum_copy_list_kernel, dim3(kLeftoverWgs), dim3(128), 0, s, d, (const uint32_t *)left,
-                                   next_left, (const uint32_t *)list, out);
-                e = hipGetLastError();
-            }
-            if (e != hipSuccess) reset_pair_counters(s);
-            if (e != hipSuccess) return e;
-            const size_t done = nrow * F;
-            return done >= n ? hipSuccess : launch_bcopy_desc(d + done, n - done, out + done, mode, img, s, 1u);
-        }
+        size_t done = 0;
+        const hipError_t e = launch_sum_desc_row4k(d, n, out, img, s, contig, &done);
+        if (e != hipSuccess) return e;
+        if (done) return done >= n ? hipSuccess : launch_bcopy_desc(d + done, n - done, out + done, mode, img, s, 1u);
     }
     return launch_fused_copy(CopySource{d}, crc, n, img, out, s, sh);
 }

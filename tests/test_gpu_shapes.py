@@ -546,6 +546,38 @@ def test_learned_contiguous_descriptors_packed(cuda, oracle, L, mode):
         assert np.array_equal(got[:m], prepared["run"][1][:m])
 
 
+@pytest.mark.parametrize("mode", [0, 1], ids=["crc", "sum"])
+@pytest.mark.parametrize("L", [128, 512])
+def test_learned_contiguous_descriptors_smallest_batch(cuda, oracle, L, mode):
+    """The two lengths the test above leaves out, in the smallest batch its routes take: 256 whole 4 KiB rows of L-byte
+    fragments in one contiguous run (kPackedMinRows: CRC in packed rows, crc_regular_kernel<kSub = L / 64>;
+    kSumRow4kMinRows: SUM on sum_row4k_desc_kernel<L / 16>), five fragments past the last whole item (the count split
+    after the fast route) and one fragment in the middle a byte short, at an index the census does not sample: the
+    learned shape stays "one contiguous run" and the fragment's item goes on the leftover list.  The first call
+    launches the census, the later ones run what it learned; every call vs the oracle."""
+    import torch
+
+    dv = _dv()
+    n = 256 * 4096 // L + 5
+    sampled = set(int(x) for x in np.arange(64) * n // 64)
+    odd = next(i for i in range(n // 2, n) if i not in sampled)
+    lens = np.full(n, L, np.uint64)
+    lens[odd] = L - 1
+    offs = np.arange(n, dtype=np.uint64) * np.uint64(L)
+    base = torch.empty(n * L, dtype=torch.uint8, device=cuda)
+    dv.fill_stream(base, seed=811 + L)
+    part = np.full(n, 0xFFFFFFFF, np.uint64)
+    descs = dv.make_descs(base, offs, lens, part)
+    want = oracle.desc_batch(base.cpu().numpy(), offs, lens.astype(np.uint32),
+                             part.astype(np.uint32) if mode == 0 else None, mode)
+    stream = torch.cuda.Stream(device=cuda)
+    with torch.cuda.stream(stream):
+        for i in range(4):
+            got = dv.as_u32(dv.frag_csum_batch(descs, mode=mode, stream=stream))
+            bad = np.nonzero(got != want)[0]
+            assert bad.size == 0, (i, bad[:8].tolist())
+
+
 def test_config_a_shape_descriptors_digest(cuda):
     """Config A's workload (1M x 1 KiB, stream seed 1) as one descriptor per fragment, after the census has seen
     it (packed rows): BASELINE.md's digest feb61101 / 41fadf13."""
